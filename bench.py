@@ -9,12 +9,17 @@ without a launcher — started by bench.py itself before any GPU call, see launc
 partitioned by the C++ partitioner (multilevel or RCB, whichever gives the smaller largest halo) across the N ranks, ghost states exchanged by RCCL (grouped send/recv over xGMI) inside
 every RHS call; value = NumEle_total x K / max-over-ranks time ("scaling": "strong": the 10M mesh is fixed).
 
-At N > 1 (and with --partition-1) every rank's DY is then checked bit for bit against a full-mesh single-GPU
-handle on its own device (`parity_vs_1gpu`); a fatal error flag on any rank (incl. a timed-out halo poll) or a
-parity miss ends the run with a non-zero status and no result line.
+A plain run sets up, settles and warms up, times the K steps, writes ydot of the last timed step with
+--dump-outputs DIR, and prints ONE JSON line on rank 0: value, ms_per_step and the roofline of the dominant kernel
+(shud_ele_kernel, HIP-event timed inside the timed steps on the stream it runs on).  A fatal error flag on any rank
+(incl. a timed-out halo poll) ends the run with a non-zero status and no result line.
 
-Prints ONE JSON line on rank 0 with roofline (dominant kernel: shud_ele_kernel, HIP-event timed on the
-stream it runs on) and cpu_baseline (the CPU restatement oracle on this host's cores, bounded sample).
+--full adds everything measured or checked beside that value, each in the same line: the STREAM and fp64-VALU
+probes, the host-vector eval, the device integrator, the many-class layouts, the ET prelude, the end-to-end shud_gpu
+run and cpu_baseline (the CPU restatement oracle on this host's cores, bounded sample); at N > 1 (and with
+--partition-1) every rank's DY is then also checked bit for bit against a full-mesh single-GPU handle on its own
+device (`parity_vs_1gpu`; a parity miss ends the run with a non-zero status and no result line) and the halo
+exchange is timed serialized.
 """
 import argparse
 import json
@@ -204,6 +209,13 @@ def main():
                          "single-GPU handle")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher test: each rank reports RANK / WORLD_SIZE and exits before touching the GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline value: STREAM / fp64-VALU probes, host-vector eval, "
+                         "integrator, many-class layouts, ET prelude, end-to-end shud_gpu run, CPU baseline; at N > 1 "
+                         "(and --partition-1) the bit-identity check against one GPU and the serialized halo timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write ydot of the last timed RHS evaluation to DIR/ydot.npy (float64; "
+                         "a fixed seeded sample of its entries when it is larger than the dump limit)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -293,8 +305,8 @@ def main():
     # the STREAM probes (~50 ms of full-bandwidth traffic) run before the warm-up: the clock transient a cold
     # GPU goes through in its first ~20 ms of load (element kernel 0.62 -> 0.74 -> 0.62 ms, profiles/r02/kt) then
     # falls outside the K timed evals instead of inside a short K = 20 window
-    sp = stream_probe(local) if world == 1 else {}
-    vp = valu_probe(local) if world == 1 else {}
+    sp = stream_probe(local) if args.full and world == 1 else {}
+    vp = valu_probe(local) if args.full and world == 1 else {}
     hb("settle")
     ts = time.perf_counter()
     for _ in range(args.settle):
@@ -365,8 +377,10 @@ def main():
         print(f"[bench] rank {rank}: fatal error flags 0x{fatal:x} (this rank: {err}) — no result", file=sys.stderr,
               flush=True)
         sys.exit(3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dy_t, rank, world)
     parity = None
-    if (world > 1 or args.partition_1) and not args.no_parity:
+    if args.full and (world > 1 or args.partition_1) and not args.no_parity:
         hb("parity")
         parity = parity_vs_1gpu(h, gm, y_glob, part, mode, local, stream, yp, dyp, dy_t, dist if world > 1 else None)
         if not parity["ok"]:
@@ -377,7 +391,7 @@ def main():
     # stream); a partitioned handle also gets a serialized per-phase breakdown (halo exchange alone)
     per = {"shud_ele_kernel": ms_ele_loop, "shud_riv_kernel": ms_riv_loop}
     ms_eval = ms_eval_loop
-    if world > 1 and args.profile_reps > 0:
+    if args.full and world > 1 and args.profile_reps > 0:
         _, per_ser = h.time_kernels(0.0, yp, dyp, args.profile_reps)
         # pack + grouped send/recv alone (serialized, no overlap), slowest rank
         th = torch.tensor([float(per_ser.get("halo_exchange") or 0.0)], dtype=torch.float64, device=f"cuda:{local}")
@@ -489,8 +503,10 @@ def main():
             print(f"[bench] {key} failed: {e!r}", file=sys.stderr, flush=True)
             out[key] = {"error": repr(e)}
 
-    hb("side")
-    if not args.no_host_vectors and world == 1:
+    side_on = args.full and world == 1
+    if side_on:
+        hb("side")
+    if side_on and not args.no_host_vectors:
         def host_vectors():
             y_h = np.ascontiguousarray(y_loc)
             dy_h = np.empty_like(y_h)
@@ -511,24 +527,24 @@ def main():
         return hh
     # the integrator first, on the default handle: its ~25 NY-long vectors are then allocated the way a SHUD run
     # allocates them (at startup), not into device memory the many-class handles just fragmented
-    if world == 1 and not args.no_ode:
+    if side_on and not args.no_ode:
         def integrator():
             h.set_step_inputs()        # the state a fresh handle starts from (step inputs + carried state reset)
             h.eval_device(0.0, yp, dyp)
             return ode_timing(h, y_glob, ms_eval, warm_steps=int(os.environ.get("SHUD_BENCH_ODE_WARM", "0")))
         side("integrator", integrator)
-    if world == 1 and not args.no_many_class:
+    if side_on and not args.no_many_class:
         h.close()                      # free the default handle's device memory first
         h = None
         side("many_class", lambda: many_class_timing(gm, y_glob, mode, local, args.steps, max(3, args.settle)))
-    if world == 1 and not args.no_et:
+    if side_on and not args.no_et:
         if h is None:
             h = fresh_handle()
         side("et_prelude", lambda: et_prelude_timing(h, gm))
-    if world == 1 and rank == 0 and args.e2e_ele > 0:
+    if side_on and rank == 0 and args.e2e_ele > 0:
         side("end_to_end", lambda: e2e_timing(args.e2e_ele))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if side_on and rank == 0 and not args.no_cpu_baseline:
         side("cpu_baseline", lambda: cpu_baseline(gm, y_glob, mode, args.cpu_seconds))
     if world > 1:
         dist.barrier()
@@ -543,6 +559,27 @@ def main():
     if arm:
         import faulthandler
         faulthandler.cancel_dump_traceback_later()
+
+
+DUMP_MAX_ENTRIES = 4_000_000     # float64 entries over all ranks (32 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, dy_t, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, ydot of that RHS evaluation
+    (device-resident, read back here), as float64 in DIR/ydot.npy (N > 1: each rank's local ydot in
+    DIR/ydot_rank<R>.npy).  A vector longer than DUMP_MAX_ENTRIES / N entries is written as a fixed sample: the
+    entries at the sorted indices default_rng(DUMP_SEED).choice(len, DUMP_MAX_ENTRIES // N, replace=False), the
+    same in every run, so two builds are compared entry for entry."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n, cap = dy_t.numel(), DUMP_MAX_ENTRIES // world
+    if n > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+        a = dy_t[torch.from_numpy(idx).to(dy_t.device)].cpu().numpy()
+    else:
+        a = dy_t.cpu().numpy()
+    np.save(os.path.join(dirname, "ydot.npy" if world == 1 else f"ydot_rank{rank}.npy"), a.astype(np.float64))
 
 
 def parity_vs_1gpu(h, gm, y_glob, part, mode, local, stream, yp, dyp, dy_t, dist, calls=2):

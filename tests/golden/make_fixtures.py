@@ -1,5 +1,5 @@
-"""Regenerate the committed fixtures from the reference's own input data (run in the dev container,
-where /root/reference exists; the GPU box only reads the outputs).
+"""Regenerate the committed fixtures from the reference's own input data (the archives under tests/golden/input/,
+or a reference checkout's input directory given in SHUD_REF_INPUT; the tests only read the outputs).
 
 Writes:
   shud-up_amd/shud_rhs/data/ccw_tables.npz  ccw soil/geol/lc/river-type tables, calibration and the
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "shud-up_amd"))
 from shud_rhs import shudio  # noqa: E402
 
-REF = "/root/reference/input"
+REF = os.environ.get("SHUD_REF_INPUT")
 
 
 def projects(names):
@@ -51,6 +51,14 @@ def main():
 
 
 if __name__ == "__main__":
+    if REF is None:
+        import tempfile
+        import zipfile
+        tmp = tempfile.TemporaryDirectory()
+        for name in ("ccw", "heihe", "qhh"):
+            with zipfile.ZipFile(os.path.join(HERE, "input", f"{name}.zip")) as z:
+                z.extractall(tmp.name)
+        REF = os.path.join(tmp.name, "input")
     if len(sys.argv) > 1:
         projects(sys.argv[1:])
     else:

@@ -1,8 +1,9 @@
 """The C++ host above the device path (libshud_host.so, include/shud_host.h), on CPU.
 
 * Readers + Model_Data::initialize + LoadIC restated in C++ equal the Python restatement (shud_rhs/shudio.py,
-  which built the committed fixtures) bit for bit on the reference's own inputs (ccw, heihe with END 9000, qhh;
-  skipped where /root/reference is absent) and on a synthetic project written in SHUD text formats.
+  which built the committed fixtures) bit for bit on the reference's own inputs (ccw, heihe with END 9000, qhh:
+  the files the readers open, one archive each under tests/golden/input/, see its README.md) and on a synthetic project
+  written in SHUD text formats.
 * Forcing: zero-order hold of every series exactly as _TimeSeriesData::movePointer/getX (TimeSeriesData.cpp),
   the missing-data exit, and the TSR bucket (MD_ET.cpp:60-136) with solar samples equal to an independent
   pure-Python restatement of solarPosition/TimeContext (tests/solar_py.py) bit for bit.
@@ -17,9 +18,20 @@ import numpy as np
 import pytest
 
 import solar_py
+from conftest import GOLDEN
 from shud_rhs import abi, host, shudio, synth
 
-REF_INPUT = "/root/reference/input"
+
+@pytest.fixture(scope="session")
+def ref_root(tmp_path_factory):
+    """the three example projects unpacked as <root>/input/<prj>/: <prj>.tsd.forc names its forcing files as
+    ./input/<prj>/..., relative to the directory the reference runs from"""
+    import zipfile
+    root = tmp_path_factory.mktemp("ref")
+    for prj in ("ccw", "heihe", "qhh"):
+        with zipfile.ZipFile(os.path.join(GOLDEN, "input", f"{prj}.zip")) as z:
+            z.extractall(root)
+    return str(root)
 
 
 def _diff(a, b):
@@ -42,11 +54,9 @@ def _diff(a, b):
 
 
 @pytest.mark.parametrize("prj,end", [("ccw", -1), ("heihe", 9000), ("qhh", -1)])
-def test_reader_matches_python_restatement(prj, end):
-    indir = os.path.join(REF_INPUT, prj)
-    if not os.path.isdir(indir):
-        pytest.skip("reference inputs absent")
-    P = host.Project(indir, prj, cwd="/root/reference", end_day=end)
+def test_reader_matches_python_restatement(prj, end, ref_root):
+    indir = os.path.join(ref_root, "input", prj)
+    P = host.Project(indir, prj, cwd=ref_root, end_day=end)
     m = P.model()
     ref, ex = shudio.load_project(indir, prj)
     assert _diff(m, ref) == []
@@ -78,18 +88,16 @@ def test_synthetic_project_round_trip(tmp_path):
     assert np.allclose((n * n).sum(0), 1.0, rtol=0, atol=1e-15) and np.all(n[2] >= 0)
 
 
-def test_control_and_print_controls_ccw():
-    indir = os.path.join(REF_INPUT, "ccw")
-    if not os.path.isdir(indir):
-        pytest.skip("reference inputs absent")
-    P = host.Project(indir, "ccw", cwd="/root/reference")
+def test_control_and_print_controls_ccw(tmp_path, ref_root):
+    indir = os.path.join(ref_root, "input", "ccw")
+    P = host.Project(indir, "ccw", cwd=ref_root)
     c = P.control()
     # ccw.cfg.para: MAX_SOLVER_STEP 10, LSM_STEP 60, INIT_SOLVER_STEP 1, END 1827, RELTOL/ABSTOL 1e-4
     assert (c["solver_step"], c["et_step"], c["init_step"], c["reltol"], c["abstol"]) == (10, 60, 1, 1e-4, 1e-4)
     assert c["end_time"] == 1827 * 1440 and c["num_steps"] == 1827 * 144
     assert (c["forc_start_time"], c["num_forc"], c["terrain_radiation"]) == (20000101, 1, 1)
     assert (c["solar_lon_deg"], c["solar_lat_deg"]) == (-122.71, 39.195)
-    outs = P.outputs("/tmp/out")
+    outs = P.outputs(str(tmp_path / "out"))
     names = [os.path.basename(o["basename"]) for o in outs]
     # initialize_output order for ccw's DT_* keys (all 1440)
     assert names == ["ccw.eleysnow", "ccw.eleysurf", "ccw.eleyunsat", "ccw.eleygw", "ccw.elevprcp",

@@ -3,7 +3,7 @@
 #   bash tools/gpu_run.sh OUTDIR STEP [STEP ...]
 # steps (each under its own timeout; the first failure ends the call):
 #   suite        pytest -m gpu (full), log + durations        smoke     __graft_entry__.smoke()
-#   bench        the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
+#   bench        the whole bench line: bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   quick        RHS-only bench line (no CPU baseline / ET / integrator / e2e)
 #   quickab:L1,L2  the RHS-only bench line for the production lib and each A/B lib, twice
 #   abv:V1,V2    tools/ab_variants.py --variants V1,V2 (e.g. pk,pkR) on the production lib, 9 rounds
@@ -35,7 +35,7 @@ for step in "$@"; do
       rest="${step#abtest:}"; lib="${rest%%:*}"; expr="${rest#*:}"
       SHUD_RHS_LIB=$PWD/shud-up_amd/build/ab/libshud_rhs_$lib.so timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread -k "$expr" > "$O/pytest_ab_$lib.log" 2>&1 ;;
     smoke) timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
-    bench) timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err" ;;
+    bench) timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err" ;;
     quick) timeout -k 10 300 python bench.py $A --steps 20 --warmup 5 > "$O/quick.json" 2> "$O/quick.err" ;;
     quickab:*)                  # quickab:L1,L2 -> RHS-only bench line for the production lib and each A/B lib, 2 rounds
       libs="${step#quickab:}"
@@ -63,7 +63,7 @@ for step in "$@"; do
       for f in prod ${libs//,/ }; do echo "$f $(tail -n 1 "$O/ab_$f.log")"; done > "$O/ab_summary.log" ;;
     odeab:*)
       libs="${step#odeab:}"
-      B="--no-cpu-baseline --no-et --no-many-class --no-host-vectors --e2e-ele 0 --steps 5 --warmup 1"
+      B="--full --no-cpu-baseline --no-et --no-many-class --no-host-vectors --e2e-ele 0 --steps 5 --warmup 1"
       for rep in 1 2; do
         for n in prod ${libs//,/ }; do
           if [ $n = prod ]; then L=""; else L=$PWD/shud-up_amd/build/ab/libshud_rhs_$n.so; fi
@@ -92,8 +92,8 @@ for step in "$@"; do
       timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$O/tcc" -o run -- python3 bench.py $A --steps 5 --warmup 1 > "$O/tcc.log" 2>&1
       python3 tools/pmc_counters.py "$O/tcc" ele_kernel riv_kernel > "$O/tcc_summary.txt" ;;
     sq) timeout -k 10 400 bash tools/sq_counters.sh "$O" > /dev/null ;;
-    ode) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_ode" -o run -- python3 bench.py --no-cpu-baseline --no-et --no-many-class --no-host-vectors --e2e-ele 0 --steps 5 --warmup 1 > "$O/bench_ode_kt.json" 2> "$O/bench_ode_kt.err" ;;
-    part1) timeout -k 10 300 python bench.py $A --partition-1 --steps 20 > "$O/bench_partition1.json" 2> "$O/bench_partition1.err" ;;
+    ode) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_ode" -o run -- python3 bench.py --full --no-cpu-baseline --no-et --no-many-class --no-host-vectors --e2e-ele 0 --steps 5 --warmup 1 > "$O/bench_ode_kt.json" 2> "$O/bench_ode_kt.err" ;;
+    part1) timeout -k 10 300 python bench.py --full $A --partition-1 --steps 20 > "$O/bench_partition1.json" 2> "$O/bench_partition1.err" ;;
     rank) timeout -k 10 400 python tools/rank_timing.py > "$O/rank_timing.json" 2> "$O/rank_timing.err" ;;
     rankab:*)                   # rankab:L1,L2 -> 8-way rank timing for the production lib and each A/B lib
       libs="${step#rankab:}"
