@@ -631,7 +631,8 @@ static int build_packed(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *
                 const size_t a = (size_t)k * NE + i, b = (size_t)kk * NE + v;
                 const double ar = m->avg_rough[a];
                 if (memcmp(&m->edge[a], &m->edge[b], 8) || memcmp(&m->dist2nabor[a], &m->dist2nabor[b], 8) ||
-                    memcmp(&m->depression[i], &m->depression[v], 8) || memcmp(&ar, &m->avg_rough[b], 8) ||
+                    (m->depression && memcmp(&m->depression[i], &m->depression[v], 8)) ||   // NULL: 0.0002 everywhere
+                    memcmp(&ar, &m->avg_rough[b], 8) ||
                     !(ar > 0. && std::isfinite(ar)) || lake_of(i) || lake_of(v))
                     continue;
                 pub[v] = (signed char)kk;

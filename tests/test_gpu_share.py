@@ -121,7 +121,7 @@ def test_share_nonfinite_heads(kind, oracle_mod, monkeypatch):
         y[2 * NE + k] = np.nan
     else:
         y[k] = np.inf
-        y[k[:3] + 1] = np.inf                          # neighbours both infinite: inf - inf = NaN head difference
+        y[m.nabr.reshape(3, -1)[:, k[:3]].max(0)] = np.inf   # a real neighbour too: inf - inf = NaN head difference
     ga, ea = _run(a, y)
     gb, eb = _run(b, y)
     _, code, idx, ekind = o.eval(0.0, y)
