@@ -94,8 +94,33 @@ inline bool cdiv_divisor_ok(double b) {
 // most classes one workgroup stages in LDS (128 x 27 x 8 B = 27 KiB)
 constexpr int kLdsClassMax = 128;
 // elements per workgroup of the packed element kernel (shud_ele_packed.hip kEleBS): the tiles the host's edge-sharing
-// assignment (shud_rhs.cpp, seg_first bits 26-29) pairs elements within
+// assignment (shud_rhs.cpp, seg_first bits 26-30) pairs elements within
 constexpr int kShareTile = 256;
+// Evaluation order (seg_first bits 26-30 of an element the sharing assignment covers): the element's three edges are
+// stored — meta.{x,y,z} and the three ged planes — in the order the sharing kernel evaluates them, stored slot s
+// holding reference slot e_s.  Bits 26-27: the stored slot that holds reference slot 0; bit 28: of the other two
+// stored slots, ascending, the first holds reference slot 2 (else 1).  Bit 29: stored slot 0 is a publication; bit
+// 30: stored slot 2 is received.  All zero: the reference order, nothing shared (every other element and handle).
+constexpr int kEvoShift = 26;
+constexpr unsigned kEvoPub0 = 1u << 29, kEvoRcv2 = 1u << 30;
+// order bits (seg_first >> kEvoShift) of the evaluation order e[s] = the reference slot in stored slot s
+inline unsigned evo_encode(const int e[3]) {
+    const int s0 = e[0] == 0 ? 0 : e[1] == 0 ? 1 : 2;
+    const int lo = s0 == 0 ? 1 : 0;
+    return (unsigned)s0 | (e[lo] == 2 ? 4u : 0u);
+}
+// the stored slot that holds reference slot j
+__host__ __device__ inline int evo_stored(unsigned bits, int j) {
+    const int s0 = (int)(bits & 3u), lo = s0 == 0 ? 1 : 0, hi = s0 == 2 ? 1 : 2;
+    const bool sw = (bits & 4u) != 0;
+    return j == 0 ? s0 : (j == 1) != sw ? lo : hi;
+}
+// the reference slot that stored slot s holds
+__host__ __device__ inline int evo_ref(unsigned bits, int s) {
+    const int s0 = (int)(bits & 3u), lo = s0 == 0 ? 1 : 0;
+    const bool sw = (bits & 4u) != 0;
+    return s == s0 ? 0 : (s == lo) != sw ? 1 : 2;
+}
 // the parked DY tail of the packed element kernel (shud_ele_packed.hip LSP): kLspN doubles + one int per thread
 // beside the ntab-double class + pow tables, taken while a workgroup's LDS stays <= kLspLdsMax (7 per CU)
 constexpr int kLspN = 5;
@@ -128,10 +153,12 @@ struct DevPacked {
     const double2 *zz;      // {z_surf, z_bottom}  (aquifer_depth == z_surf - z_bottom, checked at create)
     const int4 *meta;       // {nabr0, nabr1, nabr2, cf}: cf bits 0-7 iBC (int8), 8-9 iSS class,
                             //   10-15 #river segments, 16-30 class id, 31 lake element
-                            //   (zz and meta.w are neighbour-gathered)
-    const double2 *ged;     // [3][NE] edge-major {edge_j, dist2nabor_j}
+                            //   (zz and meta.w are neighbour-gathered); the three neighbours in stored-slot
+                            //   order (kEvoShift above: the reference order unless the element shares edges)
+    const double2 *ged;     // [3][NE] edge-major {edge_j, dist2nabor_j}, planes in the same stored-slot order
     const double *area;
-    int *seg_first;         // bits 0-30: first element-sorted segment of the element; bit 31: t_lai > ZERO
+    int *seg_first;         // bits 0-25: first element-sorted segment of the element (0-30 on handles without edge
+                            //   sharing); bits 26-30: evaluation order (kEvoShift); bit 31: t_lai > ZERO
                             //   (f_etFlux's only use of LAI, MD_ET.cpp:381; rewritten with the step inputs)
     const double2 *sg_lc;   // [NS] element-sorted segments: {length, Cwr}
     const int *sg_r;        // [NS] the segment's (local) reach; with rrec [2 * local reaches]

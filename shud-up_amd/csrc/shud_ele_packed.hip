@@ -101,9 +101,7 @@ constexpr int kEleWavesOf(bool lct, int lspk, bool gh, bool lake, int hyb, bool 
 }
 constexpr int kEleBS = 256;       // elements per workgroup
 static_assert(kEleBS == kShareTile, "edge sharing pairs elements within one workgroup's tile");
-static_assert(2 * kEleBS <= kPowTabDoubles, "edge-sharing slots fit the pow tables' LDS region");
-// an edge-sharing slot's "evaluate it yourself" mark: a signalling NaN, which no arithmetic result is
-constexpr uint64_t kShareVoid = 0x7ff0000000000001ull;
+static_assert(2 * kEleBS * 8 + kEleBS <= kPowTabDoubles * 8, "edge-sharing slots fit the pow tables' LDS region");
 // f_etFlux's three conditions (negative flux, NaN, eta > 2 ETP) are collected in a lane bit mask and reported together —
 // one ballot per wave when none fired (the common case) instead of three; the same flags, first indices and warning
 // count (atomics commute).  (Deferring all five conditions to the end of the body kept the mask live across the edge
@@ -178,6 +176,15 @@ __device__ __forceinline__ void tab_store(const DevPacked &p, const double (&tv)
 // passed by the launcher, so no workgroup reads the grid size from the dispatch packet at its start
 __device__ __forceinline__ int tile_of(int per8, int b) { return (b & 7) * per8 + (b >> 3); }
 __device__ __forceinline__ int tile_of(int per8) { return tile_of(per8, (int)blockIdx.x); }
+// A wave of an edge-sharing workgroup whose lanes are all past the end of the mesh (a partial last tile, the blocks
+// that round the grid up to a multiple of 8) still meets the sharing body's two barriers (ele_body, SH) before it
+// ends, so those barriers never count on ended waves being left out.  A partly active wave reaches them in ele_body.
+__device__ __forceinline__ bool share_idle_wave(bool act) {
+    if (__builtin_amdgcn_ballot_w64(act)) return false;
+    __syncthreads();
+    __syncthreads();
+    return true;
+}
 
 // QrivDown pre-pass (DevPacked::qdown): nb_q workgroups of the last element launch of an eval compute every local
 // reach's QrivDown (MD_RiverFlux.cpp:5-63; a function of y only, computed once per reach as MD_f.cpp:41-43 does)
@@ -236,6 +243,7 @@ shud_ele_kernel_packed(DevMesh m, DevPacked p, YView Y, double *__restrict__ dy,
         tab_store<kEleBS>(p, tv, lct);
         __syncthreads();
     }
+    if (kShareOn(LCT, GH, LAKE, HYB, DIAG) && LSPK != 0 && share_idle_wave(act)) return;
     if (act) ele_body<MODE, OPEN, DIAG, FU1, LCT, LAKE, GH, HYB, LCT ? LSPK : 0>(m, p, Y, dy, i, cur, dg, lk, lct, own);
 }
 
@@ -283,7 +291,7 @@ __device__ __forceinline__ void halo_wait(const DevMesh &m, const HaloWait &hw, 
     report_w(m.err, late, 0x80u, 7, i);                      // SHUD_EF_HALO_WAIT
 }
 template <int MODE, bool OPEN, bool FU1, int LSPK = 0>
-__global__ void __launch_bounds__(256, kEleWaves)
+__global__ void __launch_bounds__(256, (LSPK && FU1 && !OPEN) ? kEleWavesSh : kEleWaves)   // (72 VGPRs, no spills)
 shud_ele_kernel_packed_fold(DevMesh m, DevPacked p, YView Y, double *__restrict__ dy, int n_int, int n_all, int cur,
                             DevDiag dg, int per8, int nb_int, HaloWait hw, int nb_q, int q0) {
     extern __shared__ double lct[];
@@ -304,6 +312,7 @@ shud_ele_kernel_packed_fold(DevMesh m, DevPacked p, YView Y, double *__restrict_
         if (act) own = load_own<FU1, false>(p, Y, i, cur);
         tab_store<256>(p, tv, lct);
         __syncthreads();
+        if (LSPK != 0 && share_idle_wave(act)) return;
         if (act) ele_body<MODE, OPEN, false, FU1, true, false, false, 0, LSPK>(m, p, Y, dy, i, cur, dg, lk, lct, own);
         return;
     }
@@ -316,7 +325,8 @@ shud_ele_kernel_packed_fold(DevMesh m, DevPacked p, YView Y, double *__restrict_
     if (act) own = load_own<FU1, true>(p, Y, i, cur);
     tab_store<256>(p, tv, lct);
     __syncthreads();
-    if (act) ele_body<MODE, OPEN, false, FU1, true, false, true, 0, LSPK>(m, p, Y, dy, i, cur, dg, lk, lct, own);
+    // (LSP = 2: these tiles start at n_int, past the elements stored in evaluation order — nothing to decode)
+    if (act) ele_body<MODE, OPEN, false, FU1, true, false, true, 0, LSPK ? 2 : 0>(m, p, Y, dy, i, cur, dg, lk, lct, own);
 }
 // Producer: the halo's bytes were written by earlier kernels of the comm stream (pack + RCCL, or the test's copy
 // kernel), complete before this one starts; the flag store follows an agent-scope release with an explicit
@@ -424,10 +434,10 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
     }
 
     const int sfl = own.sfl;
-    // bits 26-29: edge sharing (SH), 31: LAI.  The host assigns sharing bits only to handles that take the LSP
-    // instantiations (lsp_lds_bytes), without lakes or the hybrid layout, so the plain LDS-table, big-table, lake and
-    // hybrid instantiations never see them and keep the 31-bit mask (the 26-bit one costs the plain LDS-table
-    // kernel 6 VGPRs: 80 -> 86, 6 -> 5 waves)
+    // bits 26-30: the evaluation order of an element that shares edges (shud_dev.h kEvoShift), 31: LAI.  The host
+    // assigns them only to handles that take the LSP instantiations (lsp_lds_bytes), without lakes or the hybrid
+    // layout, so the plain LDS-table, big-table, lake and hybrid instantiations never see them and keep the 31-bit
+    // mask (the 26-bit one costs the plain LDS-table kernel 6 VGPRs: 80 -> 86, 6 -> 5 waves)
     const int sfirst = sfl & ((LSP || DIAG || !LCT) ? 0x03ffffff : 0x7fffffff);
     const bool lai_on = sfl < 0;                       // bit 31: t_lai > ZERO (set with the step inputs)
     const int iss = cf_iss(cf), nseg = cf_nseg(cf);
@@ -566,14 +576,21 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
     const double area = ldnt(at(p.area, o8));          // in flight across the edge loop
     const int n_edges = is_lake ? 0 : 3;               // lake elements: fun_Ele_lakeHorizon, all zero
     constexpr bool SH = kShareOn(LCT, GH, LAKE, HYB, DIAG) && LSP != 0 && BS == kEleBS;   // edge sharing, below
-    auto edge = [&](int j, double &qsf, double &q, uint32_t &sh) __attribute__((always_inline)) {
-        const int nb = j == 0 ? mt.x : j == 1 ? mt.y : mt.z;
+    // DEC: an instantiation without sharing that can run on a handle whose elements are stored in evaluation order
+    // (the diagnostic replay, the ghost launches of a partition): it walks the reference slots and finds each one's
+    // stored slot; on every other handle the order bits are zero and the stored slot is the reference slot
+    // (LSP = 2: the folded launch's boundary tiles, which start past those elements)
+    constexpr bool DEC = !SH && LCT && !LAKE && HYB == 0 && BS == kEleBS && (LSP == 1 || DIAG);
+    [[maybe_unused]] const uint32_t evo = (uint32_t)sfl >> kEvoShift;   // order bits 0-2, bit 4: slot 2 is received
+    // edge(s, j): the edge in stored slot s, which is reference slot j (SH: s is a literal and j is derived where needed)
+    auto edge = [&](int s, int j, double &qsf, double &q, uint32_t &sh) __attribute__((always_inline)) {
+        const int nb = s == 0 ? mt.x : s == 1 ? mt.y : mt.z;
         const int nc = nb >= 0 ? nb : i;                  // boundary edge: harmless in-bounds loads
         // (edge 0's loads issued right after the own record instead — held through the vertical physics — took
         // the kernel to 96 VGPRs with spills and measured 0.707 vs 0.617 ms, profiles/r03/ab_prologue/)
         const uint32_t n16 = (uint32_t)nc << 4, n8 = (uint32_t)nc << 3;
-        // (a 32-bit byte offset: j is per lane under SH, and a 64-bit pointer per lane cost a spilled VGPR and +3 %)
-        const double2 g = ldnt2(at(p.ged, o16 + (uint32_t)j * ((uint32_t)NEl << 4)));
+        // (a 32-bit byte offset: s is per lane under DEC, and a 64-bit pointer per lane cost a spilled VGPR and +3 %)
+        const double2 g = ldnt2(at(p.ged, o16 + (uint32_t)s * ((uint32_t)NEl << 4)));
         const double2 nzz = *at(p.zz, n16);
         const int ncf = *at((const int *)p.meta + 3, n16);
         const double nsf_raw = GH ? Y.sf(nc) : *at(Y.y, n8);
@@ -641,7 +658,7 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
             }
             if constexpr (SH) sh = (mu && dh_nz ? 1u : 0u) | (!zq && dhg_nz ? 2u : 0u) | (dh_ok && dhg_ok ? 4u : 0u);
         } else if (OPEN) {
-            const double d2e = m.dist2edge[j * NEl + i];
+            const double d2e = m.dist2edge[(SH ? evo_ref(evo, s) : j) * NEl + i];   // per reference slot
             if (isf > dep_e) {
                 const double s = isf / d2e * 0.5;
                 if (s > 0.) qsf = sqrt(s) * cbrt(isf * isf * isf * isf * isf) * B / rgh_e;
@@ -662,90 +679,83 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
         sumsub += qsb;
         if (DIAG) { dg.qele_surf[j * NEl + i] = qsf; dg.qele_sub[j * NEl + i] = qsb; }
     };
-    // SH: in-tile edge sharing.  The host marks (seg_first bits 26-29) interior edges between two elements of one
-    // 256-element tile whose fluxes are exactly antisymmetric — the same edge length and Dist2Nabor bits on both sides,
-    // the same depression, a positive avgRough, no lake — and orients them so that every element publishes at most one
-    // edge and receives at most one.  From both sides the edge evaluates the same operands with dh, dhg (and the
-    // Manning slope) negated exactly, the same ym, kmean, ymg and zero-branch choices, so the neighbour's values are
-    // the publisher's negated — except where the negation would turn a +0 into -0: no Manning / a zero branch (both
-    // sides +0), dh == +0 or dhg == +0 (both sides compute the same +-0 operands).  The publisher evaluates its edge
-    // first and leaves the receiver's values in the LDS slot of its thread (the pow tables' region, dead once every
-    // wave is past satKfun), keeping the two sign bits to recover its own; the receiver takes them after a barrier, or
-    // evaluates the edge itself when the slot holds kShareVoid (a NaN head difference).  A lane without a publication
-    // evaluates one of its own edges in that first pass instead.  The remaining edges are then evaluated one per
-    // iteration with a per-lane slot (a paired element: one), so a wave makes two edge-evaluation passes instead of
-    // three unless it holds the one element per tile path that must evaluate three; the sums keep the reference's
-    // slot order.  syn-10M: 99.6 % of the elements receive an edge (profiles/r06/share/).
+    // SH: in-tile edge sharing.  The host pairs interior edges between two elements of one 256-element tile whose
+    // fluxes are exactly antisymmetric — the same edge length and Dist2Nabor bits on both sides, the same depression, a
+    // positive avgRough, no lake — and orients them so that every element publishes at most one edge and receives at
+    // most one.  From both sides the edge evaluates the same operands with dh, dhg (and the Manning slope) negated
+    // exactly, the same ym, kmean, ymg and zero-branch choices, so the neighbour's values are the publisher's negated
+    // — except where the negation would turn a +0 into -0: no Manning / a zero branch (both sides +0), dh == +0 or
+    // dhg == +0 (both sides compute the same +-0 operands).
+    // The host also stores each element's edges in the order they are evaluated (shud_rhs.cpp build_packed): stored
+    // slot 0 is the publication (else any edge), stored slot 2 the received edge (else any), so the three stages below
+    // are straight-line code with a literal slot and each reads one ged plane, coalesced:
+    //   1. every lane evaluates stored slot 0 and leaves its own values and the three sh bits in its thread's LDS slot
+    //      (the pow tables' region, dead once every wave is past satKfun); barrier;
+    //   2. every lane evaluates stored slot 1;
+    //   3. a receiver takes its publisher's values with the signs applied; a lane that receives nothing, or whose
+    //      publisher met a NaN head difference (sh bit 2 clear), evaluates stored slot 2 itself — under one ballot, so
+    //      a wave without such a lane makes two edge-evaluation passes instead of three (a tile's chain start is one).
+    // The sums are then formed in the reference's slot order through the order bits.  syn-10M: 99.6 % of the
+    // elements receive an edge (profiles/r06/share/).
     if constexpr (!SH) {
 #pragma unroll 1
         for (int j = 0; j < n_edges; j++) {
             double qsf, q;
             uint32_t sh;
-            edge(j, qsf, q, sh);
+            edge(DEC ? evo_stored(evo, j) : j, j, qsf, q, sh);
             add(j, qsf, q);
         }
     } else {
-        // xq[t], xq[kEleBS + t]: the receiver's {QeleSurf, QeleSub before fu_Sub} of thread t's published edge, or
-        // kShareVoid in the first when a head difference was NaN (the receiver then evaluates the edge itself)
+        // xq[t], xq[kEleBS + t]: thread t's own {QeleSurf, QeleSub before fu_Sub} of its stored slot 0; xf[t]: that
+        // edge's sh bits — what its receiver negates, and whether it may take the values at all
+        typedef __attribute__((address_space(3))) volatile unsigned char lds_vb;
         lds_vd *xq = (lds_vd *)(lct + p.pt_off);
+        lds_vb *xf = (lds_vb *)(lct + p.pt_off + 2 * kEleBS);
         const int tid = (int)threadIdx.x;
-        // st: bits 0-1 the published slot + 1, 2-3 the received slot + 1, 4-5 the sh signs of the thread's own LDS
-        // slot (own values = the LDS values with these signs undone), 8-10 the slots still to be taken from LDS, 12-13
-        // the first pass's slot + 1 — one register for all of it: the loop below runs at the kernel's VGPR peak
-        uint32_t st = ((uint32_t)sfl >> 26) & 15u;
-        // first pass, every lane: its published edge, or else its lowest slot that is not the received one, whose
-        // values then wait in the thread's own (unpublished) LDS slot — so an element that only receives (a tile's
-        // first) makes its two evaluations in the two passes the wave makes anyway
-        const int jr0 = (int)((st >> 2) & 3u) - 1;
-        const int j1 = (st & 3u) ? (int)(st & 3u) - 1 : (jr0 == 0 ? 1 : 0);
-        st |= (uint32_t)(j1 + 1) << 12;
         __syncthreads();                                  // every wave is past satKfun's pow-table reads
         {
             double qsf, q;
             uint32_t sh;
-            edge(j1, qsf, q, sh);
-            if (!(st & 3u)) sh = 4u;                      // not a publication: raw values, always taken back
-            xq[tid] = (sh & 4u) ? ((sh & 1u) ? -qsf : qsf) : __builtin_bit_cast(double, kShareVoid);
-            xq[kEleBS + tid] = (sh & 2u) ? -q : q;
-            st |= (sh & 3u) << 4 | ((sh & 4u) ? 1u << (8 + j1) : 0u);   // void: evaluated again below
+            edge(0, 0, qsf, q, sh);
+            xq[tid] = qsf;
+            xq[kEleBS + tid] = q;
+            xf[tid] = (unsigned char)sh;
         }
         __syncthreads();                                  // the published edges are in LDS
-        auto rthread = [&]() __attribute__((always_inline)) {   // the publisher of the received edge
-            const int jr = (int)((st >> 2) & 3u) - 1;
-            return (jr == 0 ? mt.x : jr == 1 ? mt.y : mt.z) - (i - tid);
-        };
-        if (st & 12u) {
-            const int rt = rthread();
-            if (rt >= 0 && rt < kEleBS && __builtin_bit_cast(uint64_t, (double)xq[rt]) != kShareVoid)
-                st |= 1u << (8 + ((st >> 2) & 3u) - 1);
-        }
-        auto take = [&](int mm) __attribute__((always_inline)) {
-            double qsf, q;
-            if (mm == (int)((st >> 12) & 3u) - 1) {       // the thread's own slot: undo the receiver's signs
-                const double a = xq[tid], b = xq[kEleBS + tid];
-                qsf = (st & 16u) ? -a : a;
-                q = (st & 32u) ? -b : b;
-            } else {
-                const int rt = rthread();
-                qsf = xq[rt];
-                q = xq[kEleBS + rt];
-            }
-            add(mm, qsf, q);
-        };
-#pragma unroll 1
-        for (uint32_t om = 7u & ~(st >> 8); om; om &= om - 1) {
-            const int j = __builtin_ctz(om);
-            double qsf, q;
+        double a1, b1, a2 = 0., b2 = 0.;
+        {
             uint32_t sh;
-            edge(j, qsf, q, sh);
-#pragma unroll
-            for (int mm = 0; mm < 2; mm++)
-                if ((st >> (8 + mm) & 1u) && mm < j) { take(mm); st &= ~(1u << (8 + mm)); }
-            add(j, qsf, q);
+            edge(1, 1, a1, b1, sh);
         }
-#pragma unroll
-        for (int mm = 0; mm < 3; mm++)
-            if (st >> (8 + mm) & 1u) take(mm);
+        bool own2 = true;                                 // stored slot 2 is evaluated by this lane
+        if (evo & (kEvoRcv2 >> kEvoShift)) {
+            const int rt = mt.z - (i - tid);              // the publisher's thread
+            if (rt >= 0 && rt < kEleBS) {
+                const uint32_t f = xf[rt];
+                if (f & 4u) {
+                    const double a = xq[rt], b = xq[kEleBS + rt];
+                    a2 = (f & 1u) ? -a : a;
+                    b2 = (f & 2u) ? -b : b;
+                    own2 = false;
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(own2)) {
+            if (own2) {
+                uint32_t sh;
+                edge(2, 2, a2, b2, sh);
+            }
+        }
+        // the reference's slot order: reference slot 0 is in stored slot s0; of the other two stored slots (ascending)
+        // the first holds reference slot 1 unless the swap bit says 2
+        const double a0 = xq[tid], b0 = xq[kEleBS + tid];
+        const uint32_t s0 = evo & 3u;
+        const bool sw = (evo & 4u) != 0;
+        const double la = s0 == 0 ? a1 : a0, lb = s0 == 0 ? b1 : b0;
+        const double ha = s0 == 2 ? a1 : a2, hb = s0 == 2 ? b1 : b2;
+        add(0, s0 == 0 ? a0 : s0 == 1 ? a1 : a2, s0 == 0 ? b0 : s0 == 1 ? b1 : b2);
+        add(1, sw ? ha : la, sw ? hb : lb);
+        add(2, sw ? la : ha, sw ? lb : hb);
     }
     if (DIAG && is_lake)
         for (int j = 0; j < 3; j++) { dg.qele_surf[j * NEl + i] = 0.; dg.qele_sub[j * NEl + i] = 0.; }

@@ -609,10 +609,10 @@ static int build_packed(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *
     // whose fluxes are exactly antisymmetric (same edge length and Dist2Nabor bits from both sides, same depression,
     // positive finite avgRough, neither a lake element) is evaluated by one of them and read by the other from LDS.
     // Greedy in element order: every element publishes at most one edge and receives at most one, never both
-    // directions of one edge.  seg_first bits 26-27: the published slot + 1, bits 28-29: the received slot + 1.
+    // directions of one edge.  seg_first bits 26-30 then carry the element's evaluation order (below).
     // Elements [0, lim): a single-GPU handle's all, a partitioned handle's interior prefix (its ghost-free launch
-    // tiles from element 0; the boundary launch ignores the bits), no hybrid layout; the instantiations without
-    // sharing (diagnostics, lakes, hybrid, the 1024-thread table) ignore them.
+    // tiles from element 0), no hybrid layout; the instantiations without sharing that can run on such a handle
+    // (diagnostics, ghosts) evaluate every edge themselves and only decode the order.
     const int lim = h->n_int > 0 ? h->n_int : (h->n_own == NE ? NE : 0);
     // Only for handles that take the LSP instantiations (class + pow tables small enough, no lakes, no hybrid
     // layout): the other instantiations read seg_first with a 31-bit mask (shud_ele_packed.hip ele_body).
@@ -639,7 +639,23 @@ static int build_packed(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *
                 rcv[i] = (signed char)k;
             }
         }
-        for (int i = 0; i < NE; i++) sfirst[i] |= ((pub[i] + 1) << 26) | ((rcv[i] + 1) << 28);
+        // The evaluation order (shud_dev.h kEvoShift): first the published slot (else the lowest slot that is not the
+        // received one), last the received slot (else the highest remaining one).  meta's neighbours and the ged planes
+        // are stored in that order, so every pass of the sharing kernel reads one plane, coalesced, with a literal slot;
+        // every other reader (diagnostics, ghost instantiations) goes back through evo_stored().
+        for (int i = 0; i < lim; i++) {
+            const int p = pub[i], r = rcv[i];
+            int e[3];
+            e[0] = p >= 0 ? p : (r == 0 ? 1 : 0);
+            e[2] = r >= 0 ? r : (e[0] == 2 ? 1 : 2);
+            e[1] = 3 - e[0] - e[2];
+            const int nb[3] = {meta[i].x, meta[i].y, meta[i].z};
+            meta[i].x = nb[e[0]]; meta[i].y = nb[e[1]]; meta[i].z = nb[e[2]];
+            for (int s = 0; s < 3; s++)
+                ged[(size_t)s * NE + i] =
+                    make_double2(m->edge[(size_t)e[s] * NE + i], m->dist2nabor[(size_t)e[s] * NE + i]);
+            sfirst[i] |= (int)((evo_encode(e) << kEvoShift) | (p >= 0 ? kEvoPub0 : 0u) | (r >= 0 ? kEvoRcv2 : 0u));
+        }
         h->n_shared = (int)std::count_if(rcv.begin(), rcv.end(), [](signed char r) { return r >= 0; });
     }
     int rc;
