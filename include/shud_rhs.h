@@ -264,6 +264,14 @@ int  shud_rhs_create_partitioned(const ShudMeshSoA *mesh, const ShudParamsSoA *p
                                  const ShudRhsOptions *opt, const ShudPartition *part,
                                  shud_rhs_t *out);
 
+/* ---- layout planning without a device ---- */
+typedef struct { int packed, n_classes, n_streamed, n_shared, n_int, riv_sb; } ShudLayoutInfo;
+/* What shud_rhs_create[_partitioned] would lay out for these inputs. Touches no device.
+   part may be NULL. edge_plan (NULL or [num_ele]): seg_first bits 26-30 of each element, shifted down.
+   stored_nabr (NULL or [3*num_ele], slot-major): the neighbours in stored-slot order. */
+int shud_rhs_plan_layout(const ShudMeshSoA *, const ShudParamsSoA *, const ShudRhsOptions *,
+                         const ShudPartition *, ShudLayoutInfo *, int32_t *edge_plan, int32_t *stored_nabr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,7 +94,7 @@ inline bool cdiv_divisor_ok(double b) {
 // most classes one workgroup stages in LDS (128 x 27 x 8 B = 27 KiB)
 constexpr int kLdsClassMax = 128;
 // elements per workgroup of the packed element kernel (shud_ele_packed.hip kEleBS): the tiles the host's edge-sharing
-// assignment (shud_rhs.cpp, seg_first bits 26-30) pairs elements within
+// assignment (shud_tables.cpp share_plan, seg_first bits 26-30) pairs elements within
 constexpr int kShareTile = 256;
 // Evaluation order (seg_first bits 26-30 of an element the sharing assignment covers): the element's three edges are
 // stored — meta.{x,y,z} and the three ged planes — in the order the sharing kernel evaluates them, stored slot s
@@ -127,7 +127,7 @@ constexpr int kLspN = 5;
 constexpr size_t kLspLdsMax = 23296;
 constexpr size_t lsp_lds_bytes(int ntab) { return (size_t)(ntab + kLspN * kShareTile) * 8 + kShareTile * 4; }
 // pow_tab's log + exp tables (shud_pow_tab.h: 256 x 4 + 128 x 2 doubles; SHUD_PT_COMPACT: 128 x 2.5 + 128 x 2), staged in
-// LDS after the class table (shud_rhs.cpp checks the sizes against the generated tables)
+// LDS after the class table (shud_tables.cpp checks the sizes against the generated tables)
 #ifndef SHUD_PT_COMPACT
 #define SHUD_PT_COMPACT 1
 #endif

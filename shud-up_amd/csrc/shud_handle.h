@@ -1,10 +1,11 @@
 // shud_handle.h — internal: the shud_rhs handle shared by the host runtime translation units
-// (shud_rhs.cpp: RHS; shud_et.cpp: ET-step prelude).  Not part of the C-ABI.
+// (shud_rhs.cpp: RHS; shud_tables.cpp: create-time host tables; shud_et.cpp: ET-step prelude).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "shud_dev.h"
@@ -12,7 +13,8 @@
 
 // records the message for shud_rhs_last_error_string() and returns code
 int shud_fail(int code, const char *fmt, ...);
-
+// integer switch `name` from the environment, read strictly and announced once (shud_tables.cpp)
+int env_knob(const char *name, int def, int lo, int hi);
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
@@ -55,7 +57,7 @@ struct shud_rhs {
     bool packed = false;                 // class-table / 16-byte-record layout in use (DevPacked)
     DevPacked dp{};
     int n_classes = 0;
-    int n_shared = 0;       // interior edges evaluated once (in-tile edge sharing, build_packed)
+    int n_shared = 0;       // interior edges evaluated once (in-tile edge sharing, shud_tables.cpp)
     bool fu_unit[2] = {true, true};      // fu_Surf / fu_Sub are all 1.0 (cryosphere off): not read
     bool qd_now = false;                 // this eval's element launch wrote DevPacked::qdown (river kernel reads it)
 
@@ -130,7 +132,16 @@ struct shud_rhs {
         return 0;
     }
     template <class T>
-    int upload_fill(T **p, const T *src, size_t n, T fill) {
+    int upload(const T **p, const T *src, size_t n) {      // into a read-only member of the device structs
+        T *q = nullptr;
+        const int rc = upload(&q, src, n);
+        *p = q;
+        return rc;
+    }
+    template <class T>                                     // T or const T
+    int zeros(T **p, size_t n) { return upload(p, (const std::remove_const_t<T> *)nullptr, n); }
+    template <class T, class P>                            // P: T * or const T *
+    int upload_fill(P *p, const T *src, size_t n, T fill) {
         if (src) return upload(p, src, n);
         std::vector<T> tmp(n, fill);
         return upload(p, tmp.data(), n);

@@ -14,19 +14,15 @@
 
 #include <algorithm>
 #include <climits>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "shud_handle.h"
-#define SHUD_PT_HOST_TABLES           // the pow_tab tables as host arrays, uploaded with the class table
-#include "shud_pow_tab.h"
+#include "shud_tables.h"
 
 using namespace shud;
 
@@ -51,25 +47,6 @@ int shud_fail(int code, const char *fmt, ...) {
     return code;
 }
 
-// Run-time switches read from the environment (A/B measurements and tests).  Each is parsed strictly: a value that is
-// not an integer in [lo, hi] is ignored with a warning, and a value that takes effect is announced once per process on
-// stderr — a stray variable in a user's environment cannot silently change kernel selection.
-static int env_knob(const char *name, int def, int lo, int hi) {
-    const char *v = getenv(name);
-    if (!v || !*v) return def;
-    char *end = nullptr;
-    const long x = strtol(v, &end, 10);
-    static std::vector<std::string> said;
-    const bool first = std::find(said.begin(), said.end(), std::string(name)) == said.end();
-    if (first) said.push_back(name);
-    if (*end || x < lo || x > hi) {
-        if (first) fprintf(stderr, "shud_rhs: ignoring %s=%s (expected an integer in [%d, %d])\n", name, v, lo, hi);
-        return def;
-    }
-    if (first && x != def) fprintf(stderr, "shud_rhs: %s=%ld in effect (default %d)\n", name, x, def);
-    return (int)x;
-}
-
 int shud_reset_err(shud_rhs *h) {
     DevErr z{};
     z.flags = 0;
@@ -88,176 +65,24 @@ extern "C" const char *shud_rhs_last_error_string(void) { return g_last_error.c_
 // ---------------------------------------------------------------------------------------------
 // create
 // ---------------------------------------------------------------------------------------------
-// Segments per batch in the river kernel: a wave issues SB flux gathers + its position loads per batch and runs
-// as many batches as its lane with the most segments needs; pick the batch size that issues fewer loads over the
-// owned reaches' 64-reach waves (6 or 8: 16-B + 8-B or two 16-B position loads)
-static int choose_riv_sb(const int *nseg, int nr) {
-    long long cost6 = 0, cost8 = 0;
-    for (int w = 0; w < nr; w += 64) {
-        int mx = 0;
-        for (int r = w; r < nr && r < w + 64; r++) mx = std::max(mx, nseg[r]);
-        cost6 += (long long)((mx + 5) / 6) * (6 + 2);
-        cost8 += (long long)((mx + 7) / 8) * (8 + 2);
-    }
-    return cost6 < cost8 ? 6 : 8;
-}
-
-static int build_packed(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *p, const std::vector<int> &eflags,
-                        const std::vector<int> &seg_off, const std::vector<int> &up_off,
-                        const std::vector<int> &up_idx);
-
-static int build_lakes(shud_rhs *h, const ShudMeshSoA *m, const ShudPartition *part);
+// Build the host tables (shud_tables.cpp), copy their scalars into the handle, upload, allocate the work buffers.
+// The tables go when this returns; seg_perm alone stays in the handle (diagnostics in reference segment order).
 static int build(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *p, const ShudRhsOptions *opt,
                  const ShudPartition *part) {
+    HostTables H;
+    int rc = build_tables(m, p, opt, part, &H);
+    if (rc) return rc;
+    MeshTables &T = H.mesh;
+    const PackedTables &K = H.pk;
     const int NE = m->num_ele, NR = m->num_riv, NS = m->num_seg;
-    if (NE < 0 || NR < 0 || NS < 0) return shud_fail(SHUD_ERR_ARG, "negative sizes");
     h->NE = NE; h->NR = NR; h->NS = NS;
-    h->mode = opt ? opt->mode : SHUD_MODE_SERIAL;
-    if (h->mode != SHUD_MODE_SERIAL && h->mode != SHUD_MODE_OMP) return shud_fail(SHUD_ERR_ARG, "bad mode %d", h->mode);
-    h->check_errors = opt ? opt->check_errors != 0 : true;
-    h->open = (m->close_boundary == 0);
-    h->device = opt ? opt->device : 0;
-    h->n_own = part ? part->n_own_ele : NE;
-    h->n_segghost = part ? part->n_segghost_ele : 0;
-    h->n_own_riv = part ? part->n_own_riv : NR;
-    if (h->n_own < 0 || h->n_own + h->n_segghost > NE || h->n_own_riv < 0 || h->n_own_riv > NR)
-        return shud_fail(SHUD_ERR_ARG, "partition counts inconsistent with mesh sizes");
-
-    // ---- validation (the reference exits on these at run time; we reject them up front) ----
-    if (!m->nabr || !m->area || !m->z_surf || !m->z_bottom || !m->edge || !m->dist2nabor || !m->avg_rough)
-        return shud_fail(SHUD_ERR_ARG, "missing element geometry array");
-    if (h->open && (!m->dist2edge || !m->rough)) return shud_fail(SHUD_ERR_ARG, "open boundary needs dist2edge and rough");
-    if (NR && (!m->riv_down || !m->riv_length || !m->riv_bed_slope || !m->riv_dist2down || !m->riv_avg_rough ||
-               !m->riv_depth || !m->riv_bottom_width || !m->riv_bankslope || !m->riv_ksath || !m->riv_bedthick))
-        return shud_fail(SHUD_ERR_ARG, "missing river array");
-    if (NS && (!m->seg_ele || !m->seg_riv || !m->seg_length || !m->seg_cwr)) return shud_fail(SHUD_ERR_ARG, "missing segment array");
-    const double *pp[17] = {p->aquifer_depth, p->macD, p->macKsatH, p->geo_vAreaF, p->KsatH, p->KsatV,
-                            p->infKsatV, p->hAreaF, p->macKsatV, p->ThetaS, p->ThetaR, p->Beta,
-                            p->infD, p->Sy, p->RzD, p->VegFrac, p->ImpAF};
-    for (int k = 0; k < 17; k++)
-        if (!pp[k]) return shud_fail(SHUD_ERR_ARG, "missing parameter array #%d", k);
-    for (long long q = 0; q < 3LL * NE; q++)
-        if (m->nabr[q] < -1 || m->nabr[q] >= NE) return shud_fail(SHUD_ERR_ARG, "nabr[%lld]=%d out of range", q, m->nabr[q]);
-    // lakes: on when any iLake > 0 (MD_readin.cpp:262-263); serial semantics, packed layout.  Partitioned:
-    // the plan (shud_partition.h) puts a lake's elements and bank elements on one rank and numbers its lakes
-    // locally, so every lake sum is formed from owned elements and owned or ghost reaches
-    if (m->ilake)
-        for (int i = 0; i < NE; i++)
-            if (m->ilake[i] > 0) h->lakeon = true;
-    if (h->lakeon) {
-        if (h->mode != SHUD_MODE_SERIAL)
-            return shud_fail(SHUD_ERR_UNSUPPORTED, "lakes: the OMP path has no lake physics (MD_f_omp.cpp)");
-        h->NL = m->num_lake;
-        if (h->NL <= 0 || !m->lake_bathy_off || !m->lake_bathy_y || !m->lake_bathy_a)
-            return shud_fail(SHUD_ERR_ARG, "lake elements present but no lake bathymetry (num_lake %d)", m->num_lake);
-        for (int l = 0; l < h->NL; l++)
-            if (m->lake_bathy_off[l + 1] <= m->lake_bathy_off[l])
-                return shud_fail(SHUD_ERR_ARG, "lake %d has an empty bathymetry table", l + 1);
-        for (int i = 0; i < NE; i++)
-            if (m->ilake[i] > h->NL) return shud_fail(SHUD_ERR_ARG, "element %d: iLake %d > num_lake", i, m->ilake[i]);
-    }
-    for (int r = 0; r < NR; r++) {
-        int d = m->riv_down[r];
-        if (h->lakeon && d <= -4) {               // toLake = (-3 - down) - 1 (MD_Lake.cpp:46-50)
-            if ((-3 - d) - 1 >= h->NL)
-                return shud_fail(SHUD_ERR_ARG, "reach %d flows into lake %d > num_lake", r, -3 - d);
-            continue;
-        }
-        if (d >= NR || (d < 0 && d < -4))
-            return shud_fail(SHUD_ERR_ARG, "Fatal Error: River Routing Boundary Condition Type Is Wrong! (reach %d down %d)", r, d);
-    }
-    // reach codes as the kernels see them: a reach into a lake uses the zero-depth-gradient formula (-3)
-    std::vector<int> rdown(m->riv_down, m->riv_down + NR);
-    if (h->lakeon)
-        for (int r = 0; r < NR; r++)
-            if (rdown[r] <= -4) rdown[r] = -3;
-    for (int s = 0; s < NS; s++)
-        if (m->seg_ele[s] < 0 || m->seg_ele[s] >= NE || m->seg_riv[s] < 0 || m->seg_riv[s] >= NR)
-            return shud_fail(SHUD_ERR_ARG, "segment %d references element/reach out of range", s);
-
-    // ---- packed element flags, BC column maxima ----
-    std::vector<int> eflags(NE);
-    for (int i = 0; i < NE; i++) {
-        int ibc = m->ibc ? m->ibc[i] : 0, iss = m->iss ? m->iss[i] : 0;
-        if (ibc < -32768 || ibc > 32767) return shud_fail(SHUD_ERR_ARG, "iBC out of range at %d", i);
-        eflags[i] = (ibc & 0xffff) | ((iss > 0 ? 1 : iss < 0 ? 2 : 0) << 16);
-        if (ibc > 0) h->max_col[0] = std::max(h->max_col[0], ibc);
-        if (ibc < 0) h->max_col[1] = std::max(h->max_col[1], -ibc);
-    }
-    std::vector<int> rbc(NR, 0);
-    for (int r = 0; r < NR; r++) {
-        rbc[r] = m->riv_bc ? m->riv_bc[r] : 0;
-        if (rbc[r] > 0) h->max_col[2] = std::max(h->max_col[2], rbc[r]);
-        if (rbc[r] < 0) h->max_col[3] = std::max(h->max_col[3], -rbc[r]);
-    }
-
-    // ---- segment CSR by element (stable: ascending reference index inside an element) ----
-    const int ncomp = h->n_own + h->n_segghost;
-    std::vector<int> order(NS);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m->seg_ele[a] < m->seg_ele[b]; });
-    std::vector<int> seg_off(NE + 1, 0), seg_riv(NS), pos_of(NS);
-    std::vector<double> seg_len(NS), seg_cwr(NS);
-    for (int s = 0; s < NS; s++) seg_off[m->seg_ele[s] + 1]++;
-    for (int i = 0; i < NE; i++) seg_off[i + 1] += seg_off[i];
-    for (int k = 0; k < NS; k++) {
-        int s = order[k];
-        seg_riv[k] = m->seg_riv[s];
-        seg_len[k] = m->seg_length[s];
-        seg_cwr[k] = m->seg_cwr[s];
-        pos_of[s] = k;
-    }
-    // only elements < ncomp compute their segments; segments of pure ghosts must not be needed
-    for (int s = 0; s < NS; s++)
-        if (m->seg_ele[s] >= ncomp && m->seg_riv[s] < h->n_own_riv)
-            return shud_fail(SHUD_ERR_ARG, "segment %d of an owned reach belongs to a non-computed ghost element", s);
-    h->seg_perm = order;
-    // ---- partitioned: owned elements [0, n_int) read no ghost data (all lateral neighbours owned, all their
-    // segments' reaches owned); they run while the halo exchange is in flight (eval_device) ----
-    h->n_int = 0;
-    if (part) {
-        int i = 0;
-        for (; i < h->n_own; i++) {
-            bool dep = false;
-            for (int j = 0; j < 3 && !dep; j++) dep = m->nabr[(size_t)j * NE + i] >= h->n_own;
-            for (int k = seg_off[i]; k < seg_off[i + 1] && !dep; k++) dep = seg_riv[k] >= h->n_own_riv;
-            if (dep) break;
-        }
-        h->n_int = i;
-    }
-    // ---- per owned reach: its segments (ascending reference order) and upstream reaches ----
-    std::vector<int> rseg_off(h->n_own_riv + 1, 0), rseg_pos;
-    for (int s = 0; s < NS; s++)
-        if (m->seg_riv[s] < h->n_own_riv) rseg_off[m->seg_riv[s] + 1]++;
-    for (int r = 0; r < h->n_own_riv; r++) rseg_off[r + 1] += rseg_off[r];
-    rseg_pos.resize(rseg_off[h->n_own_riv]);
-    {
-        std::vector<int> fillp(rseg_off.begin(), rseg_off.end() - 1);
-        for (int s = 0; s < NS; s++) {
-            int r = m->seg_riv[s];
-            if (r < h->n_own_riv) rseg_pos[fillp[r]++] = pos_of[s];
-        }
-        rseg_pos.resize(rseg_pos.size() + 8, 0);   // the river kernel may read a whole 8-position batch past the end
-    }
-    std::vector<int> up_off(h->n_own_riv + 1, 0), up_idx;
-    for (int r = 0; r < NR; r++) {
-        int d = m->riv_down[r];
-        if (d >= 0 && d < h->n_own_riv) up_off[d + 1]++;
-    }
-    for (int r = 0; r < h->n_own_riv; r++) up_off[r + 1] += up_off[r];
-    up_idx.resize(up_off[h->n_own_riv]);
-    {
-        // ascending reach order (MD_f.cpp:236-240); in a partition, ascending GLOBAL reach id
-        std::vector<int> fillp(up_off.begin(), up_off.end() - 1);
-        for (int r = 0; r < NR; r++) {
-            int d = m->riv_down[r];
-            if (d >= 0 && d < h->n_own_riv) up_idx[fillp[d]++] = r;
-        }
-        if (part && part->riv_gid)
-            for (int r = 0; r < h->n_own_riv; r++)
-                std::sort(up_idx.begin() + up_off[r], up_idx.begin() + up_off[r + 1],
-                          [&](int a, int b) { return part->riv_gid[a] < part->riv_gid[b]; });
-    }
+    h->mode = T.mode; h->open = T.open;
+    h->check_errors = opt ? opt->check_errors != 0 : true; h->device = opt ? opt->device : 0;
+    h->n_own = T.n_own; h->n_segghost = T.n_segghost; h->n_own_riv = T.n_own_riv; h->n_int = T.n_int;
+    h->lakeon = T.lakeon; h->NL = T.NL;
+    std::copy(T.max_col, T.max_col + 4, h->max_col);
+    h->seg_perm.swap(T.seg_perm);
+    h->packed = H.packed; h->dp = K.dp; h->n_classes = K.dp.ncls; h->n_shared = K.n_shared;
 
     // ---- device ----
     HIP_TRY(hipSetDevice(h->device));
@@ -267,577 +92,76 @@ static int build(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *p, cons
         HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         h->own_stream = true;
     }
+    // the first failure sticks: later uploads are skipped and rc is returned after the last one
+    auto up = [&](auto **dst, const auto *src, size_t n) { if (!rc) rc = h->upload(dst, src, n); };
+    auto upv = [&](auto **dst, const auto &v) { up(dst, v.data(), v.size()); };
+    auto zero = [&](auto **dst, size_t n) { if (!rc) rc = h->zeros(dst, n); };
+    auto fill = [&](auto **dst, const double *src, size_t n, double v) { if (!rc) rc = h->upload_fill(dst, src, n, v); };
+    const size_t E = (size_t)NE, E3 = 3 * E;
     DevMesh &d = h->dm;
     d.num_ele = NE;
-    int rc = 0;
-#define UP(field, src, n) if ((rc = h->upload(&field##_w, src, n))) return rc; d.field = field##_w
-    {
-        int *nabr_w, *eflags_w;
-        double *area_w, *z_surf_w, *z_bottom_w, *depression_w, *edge_w, *dist2nabor_w, *dist2edge_w, *avg_rough_w, *rough_w;
-        UP(nabr, m->nabr, 3 * (size_t)NE);
-        UP(eflags, eflags.data(), NE);
-        UP(area, m->area, NE);
-        UP(z_surf, m->z_surf, NE);
-        UP(z_bottom, m->z_bottom, NE);
-        if ((rc = h->upload_fill(&depression_w, m->depression, NE, 0.0002))) return rc;
-        d.depression = depression_w;
-        UP(edge, m->edge, 3 * (size_t)NE);
-        UP(dist2nabor, m->dist2nabor, 3 * (size_t)NE);
-        UP(avg_rough, m->avg_rough, 3 * (size_t)NE);
-        UP(dist2edge, h->open ? m->dist2edge : (const double *)nullptr, h->open ? 3 * (size_t)NE : 1);
-        UP(rough, h->open ? m->rough : (const double *)nullptr, h->open ? (size_t)NE : 1);
-    }
-    {
-        double *aq_w, *macD_w, *macKsatH_w, *vAreaF_w, *KsatH_w, *KsatV_w, *infKsatV_w, *hAreaF_w, *macKsatV_w;
-        double *ThetaS_w, *ThetaR_w, *Beta_w, *infD_w, *Sy_w, *RzD_w, *VegFrac_w, *ImpAF_w;
-        UP(aq, p->aquifer_depth, NE); UP(macD, p->macD, NE); UP(macKsatH, p->macKsatH, NE);
-        UP(vAreaF, p->geo_vAreaF, NE); UP(KsatH, p->KsatH, NE); UP(KsatV, p->KsatV, NE);
-        UP(infKsatV, p->infKsatV, NE); UP(hAreaF, p->hAreaF, NE); UP(macKsatV, p->macKsatV, NE);
-        UP(ThetaS, p->ThetaS, NE); UP(ThetaR, p->ThetaR, NE); UP(Beta, p->Beta, NE); UP(infD, p->infD, NE);
-        UP(Sy, p->Sy, NE); UP(RzD, p->RzD, NE); UP(VegFrac, p->VegFrac, NE); UP(ImpAF, p->ImpAF, NE);
-    }
-    {
-        double *net_prep_w, *pot_evap_w, *pot_tran_w, *etp_w, *lai_w, *fu_surf_w, *fu_sub_w, *ugw_stale_w, *prcp_w;
-        UP(prcp, (const double *)nullptr, NE);
-        UP(net_prep, (const double *)nullptr, NE); UP(pot_evap, (const double *)nullptr, NE); UP(pot_tran, (const double *)nullptr, NE); UP(etp, (const double *)nullptr, NE);
-        UP(lai, (const double *)nullptr, NE);
-        if ((rc = h->upload_fill(&fu_surf_w, (const double *)nullptr, NE, 1.0))) return rc;
-        d.fu_surf = fu_surf_w;
-        if ((rc = h->upload_fill(&fu_sub_w, (const double *)nullptr, NE, 1.0))) return rc;
-        d.fu_sub = fu_sub_w;
-        UP(ugw_stale, (const double *)nullptr, NE);
-        for (int k = 0; k < 2; k++) {
-            if ((rc = h->upload(&d.e_ic[k], (const double *)nullptr, NE))) return rc;
-            if ((rc = h->upload(&d.u_satn[k], (const double *)nullptr, NE))) return rc;
-        }
-    }
+    up(&d.nabr, m->nabr, E3); upv(&d.eflags, T.eflags);
+    up(&d.area, m->area, E); up(&d.z_surf, m->z_surf, E); up(&d.z_bottom, m->z_bottom, E);
+    fill(&d.depression, m->depression, E, 0.0002);
+    up(&d.edge, m->edge, E3); up(&d.dist2nabor, m->dist2nabor, E3); up(&d.avg_rough, m->avg_rough, E3);
+    if (h->open) { up(&d.dist2edge, m->dist2edge, E3); up(&d.rough, m->rough, E); }
+    else { zero(&d.dist2edge, 1); zero(&d.rough, 1); }
+    up(&d.aq, p->aquifer_depth, E); up(&d.macD, p->macD, E); up(&d.macKsatH, p->macKsatH, E);
+    up(&d.vAreaF, p->geo_vAreaF, E); up(&d.KsatH, p->KsatH, E); up(&d.KsatV, p->KsatV, E);
+    up(&d.infKsatV, p->infKsatV, E); up(&d.hAreaF, p->hAreaF, E); up(&d.macKsatV, p->macKsatV, E);
+    up(&d.ThetaS, p->ThetaS, E); up(&d.ThetaR, p->ThetaR, E); up(&d.Beta, p->Beta, E); up(&d.infD, p->infD, E);
+    up(&d.Sy, p->Sy, E); up(&d.RzD, p->RzD, E); up(&d.VegFrac, p->VegFrac, E); up(&d.ImpAF, p->ImpAF, E);
+    zero(&d.prcp, E); zero(&d.net_prep, E); zero(&d.pot_evap, E); zero(&d.pot_tran, E); zero(&d.etp, E);
+    zero(&d.lai, E); zero(&d.ugw_stale, E);
+    fill(&d.fu_surf, nullptr, E, 1.0); fill(&d.fu_sub, nullptr, E, 1.0);
+    for (int k = 0; k < 2; k++) { zero(&d.e_ic[k], E); zero(&d.u_satn[k], E); }
     for (int k = 0; k < 4; k++) {
         h->tab_len[k] = h->max_col[k] + 1;
-        if ((rc = h->upload(&h->d_tab[k], (const double *)nullptr, h->tab_len[k]))) return rc;
+        zero(&h->d_tab[k], h->tab_len[k]);
     }
     d.eybc = h->d_tab[0]; d.eqbc = h->d_tab[1]; d.rybc = h->d_tab[2]; d.rqbc = h->d_tab[3];
-    {
-        int *seg_off_w, *seg_riv_w;
-        double *seg_len_w, *seg_cwr_w;
-        UP(seg_off, seg_off.data(), NE + 1);
-        UP(seg_riv, seg_riv.data(), NS);
-        UP(seg_len, seg_len.data(), NS);
-        UP(seg_cwr, seg_cwr.data(), NS);
-        if ((rc = h->upload(&d.qseg_surf, (const double *)nullptr, NS))) return rc;
-        if ((rc = h->upload(&d.qseg_sub, (const double *)nullptr, NS))) return rc;
+    upv(&d.seg_off, T.seg_off); upv(&d.seg_riv, T.seg_riv); upv(&d.seg_len, T.seg_len); upv(&d.seg_cwr, T.seg_cwr);
+    zero(&d.qseg_surf, NS); zero(&d.qseg_sub, NS);
+    upv(&d.riv_down, T.riv_down); upv(&d.riv_bc, T.riv_bc);
+    up(&d.riv_len, m->riv_length, NR); up(&d.riv_slope, m->riv_bed_slope, NR); up(&d.riv_d2down, m->riv_dist2down, NR);
+    up(&d.riv_avg_rough, m->riv_avg_rough, NR); up(&d.riv_depth, m->riv_depth, NR); up(&d.riv_bw, m->riv_bottom_width, NR);
+    up(&d.riv_bankslope, m->riv_bankslope, NR); up(&d.riv_ksath, m->riv_ksath, NR); up(&d.riv_bedthick, m->riv_bedthick, NR);
+    upv(&d.up_off, T.up_off); upv(&d.up_idx, T.up_idx);
+    up(&d.rseg_off, T.reach_off.data(), (size_t)T.n_own_riv + 1); upv(&d.rseg_pos, T.rseg_pos);
+    if (h->packed) {
+        DevPacked &P = h->dp;
+        upv(&P.ctab, K.ctab); upv(&P.zz, K.zz); upv(&P.meta, K.meta); upv(&P.ged, K.ged); up(&P.area, m->area, E);
+        upv(&P.seg_first, K.seg_first);
+        if (P.nh) upv(&P.hv, K.hv);
+        upv(&P.sg_lc, K.sg_lc); upv(&P.sg_r, T.seg_riv); upv(&P.rrec, K.rrec);
+        zero(&P.qseg2, NS); zero(&P.s_np, E); zero(&P.s_tl, E); zero(&P.cs[0], E); zero(&P.cs[1], E);
+        if (!rc) rc = h->upload_fill(&P.s_fu, (const double2 *)nullptr, E, make_double2(1.0, 1.0));
+        upv(&P.rv, K.rv); upv(&P.rv_u, K.rv_u);
+        if (P.nqd) zero(&P.qdown, NR);
     }
-    {
-        int *riv_down_w, *riv_bc_w, *up_off_w, *up_idx_w, *rseg_off_w, *rseg_pos_w;
-        double *riv_len_w, *riv_slope_w, *riv_d2down_w, *riv_avg_rough_w, *riv_depth_w, *riv_bw_w,
-            *riv_bankslope_w, *riv_ksath_w, *riv_bedthick_w;
-        UP(riv_down, rdown.data(), NR); UP(riv_bc, rbc.data(), NR);
-        UP(riv_len, m->riv_length, NR); UP(riv_slope, m->riv_bed_slope, NR); UP(riv_d2down, m->riv_dist2down, NR);
-        UP(riv_avg_rough, m->riv_avg_rough, NR); UP(riv_depth, m->riv_depth, NR); UP(riv_bw, m->riv_bottom_width, NR);
-        UP(riv_bankslope, m->riv_bankslope, NR); UP(riv_ksath, m->riv_ksath, NR); UP(riv_bedthick, m->riv_bedthick, NR);
-        UP(up_off, up_off.data(), up_off.size()); UP(up_idx, up_idx.data(), up_idx.size());
-        UP(rseg_off, rseg_off.data(), rseg_off.size()); UP(rseg_pos, rseg_pos.data(), rseg_pos.size());
+    if (h->lakeon) {
+        DevLake &L = h->lk;
+        const LakeTables &S = H.lake;
+        L.nl = h->NL;
+        L.y_off = 3 * h->n_own + h->n_own_riv;    // [sf|us|gw|riv|lake] over owned entities
+        upv(&L.lake_of, S.lake_of); upv(&L.ele_off, S.ele_off); upv(&L.ele_idx, S.ele_idx);
+        upv(&L.bank_off, S.bank_off); upv(&L.bank_pos, S.bank_pos); upv(&L.rin_off, S.rin_off); upv(&L.rin_idx, S.rin_idx);
+        const size_t nb = m->lake_bathy_off[h->NL];
+        up(&L.bathy_off, m->lake_bathy_off, (size_t)h->NL + 1); up(&L.bathy_y, m->lake_bathy_y, nb); up(&L.bathy_a, m->lake_bathy_a, nb);
+        zero(&L.bank_qs, E3); zero(&L.bank_qg, E3);
     }
-#undef UP
-    if ((rc = build_packed(h, m, p, eflags, seg_off, up_off, up_idx))) return rc;
-    if (h->lakeon && (rc = build_lakes(h, m, part))) return rc;
-    if ((rc = h->dalloc(&h->d_err, 1))) return rc;
-    if ((rc = h->dalloc(&h->d_warn, (size_t)kWarnSlots * kWarnStride))) return rc;
+    if (rc) return rc;
+
+    // ---- work buffers ----
+    if ((rc = h->dalloc(&h->d_err, 1)) || (rc = h->dalloc(&h->d_warn, (size_t)kWarnSlots * kWarnStride))) return rc;
     d.err = h->d_err;
     HIP_TRY(hipHostMalloc((void **)&h->h_err, sizeof(DevErr), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void **)&h->h_warn, kWarnSlots * kWarnStride * sizeof(unsigned long long),
                           hipHostMallocDefault));
     if ((rc = shud_reset_err(h))) return rc;
     const size_t ny = 3 * (size_t)h->n_own + h->n_own_riv + h->NL;
-    if ((rc = h->dalloc(&h->d_y, ny))) return rc;
-    if ((rc = h->dalloc(&h->d_ydot, ny))) return rc;
-    if ((rc = h->dalloc(&h->d_scratch_dy, ny))) return rc;
-    return 0;
-}
-
-// Distinct fixed-length tuples of 64-bit words (bit patterns: two doubles are the same key when their bits are), each
-// numbered in first-seen order: open addressing over a power-of-two slot table, the tuples stored flat.  The class
-// search below runs it over every element several times per handle (one pass per candidate hybrid field set), so it
-// avoids per-element heap keys (std::string keys of 144 B cost seconds at 10M elements).
-class TupleSet {
-  public:
-    explicit TupleSet(int k) : k_(k), slots_(1024, -1) {}     // k <= 32
-    int size() const { return (int)(words_.size() / k_); }
-    const uint64_t *tuple(int id) const { return &words_[(size_t)id * k_]; }
-    // id of the tuple at p (k 8-byte words, any type: copied as bits), inserted if new
-    int insert(const void *p) {
-        uint64_t t[32];
-        memcpy(t, p, (size_t)k_ * 8);
-        if ((size_t)(size() + 1) * 2 > slots_.size()) grow();
-        size_t j = hash(t) & (slots_.size() - 1);
-        for (;; j = (j + 1) & (slots_.size() - 1)) {
-            const int id = slots_[j];
-            if (id < 0) break;
-            if (!memcmp(tuple(id), t, (size_t)k_ * 8)) return id;
-        }
-        const int id = size();
-        slots_[j] = id;
-        words_.insert(words_.end(), t, t + k_);
-        return id;
-    }
-
-  private:
-    uint64_t hash(const uint64_t *t) const {
-        uint64_t h = 0x9e3779b97f4a7c15ull;
-        for (int q = 0; q < k_; q++) {                  // splitmix64 finaliser per word, chained
-            uint64_t x = t[q] + h;
-            x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-            x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-            h = x ^ (x >> 31);
-        }
-        return h;
-    }
-    void grow() {
-        std::vector<int> old;
-        old.swap(slots_);
-        slots_.assign(old.size() * 2, -1);
-        for (int id : old) {
-            if (id < 0) continue;
-            size_t j = hash(tuple(id)) & (slots_.size() - 1);
-            while (slots_[j] >= 0) j = (j + 1) & (slots_.size() - 1);
-            slots_[j] = id;
-        }
-    }
-    int k_;
-    std::vector<int> slots_;
-    std::vector<uint64_t> words_;
-};
-
-// Packed class layout (shud_dev.h DevPacked).  Returns 0 with h->packed set, 0 with h->packed clear when
-// the mesh does not qualify (the SoA kernel is used), or an error code.
-static int build_packed(shud_rhs *h, const ShudMeshSoA *m, const ShudParamsSoA *p, const std::vector<int> &eflags,
-                        const std::vector<int> &seg_off, const std::vector<int> &up_off,
-                        const std::vector<int> &up_idx) {
-    if (!env_knob("SHUD_RHS_PACKED", 1, 0, 1)) return 0;         // 0: the SoA kernel (tests, A/B)
-    const int NE = m->num_ele;
-    if (!m->rough || NE == 0) return 0;
-    // avgRough must be the reference's 0.5*(Rough_i + Rough_nabr) / Rough_i (Element.cpp:249-265).  Owned
-    // elements only: a ghost never computes lateral fluxes, and its neighbours outside the rank's local mesh
-    // appear as boundary edges (-1) while its avgRough is the global one
-    for (int j = 0; j < 3; j++)
-        for (int i = 0; i < h->n_own; i++) {
-            const int nb = m->nabr[(size_t)j * NE + i];
-            const double want = nb >= 0 ? 0.5 * (m->rough[i] + m->rough[nb]) : m->rough[i];
-            if (!(m->avg_rough[(size_t)j * NE + i] == want)) return 0;
-        }
-    // identities the packed record relies on (else the SoA kernel runs): AquiferDepth == z_surf - z_bottom
-    // (InitElement after rmSinks, Model_Data.cpp:262-264), |iBC| fits int8, <= 63 segments per element
-    // the packed kernel addresses its element / segment streams with 32-bit byte offsets (at(), shud_ele_packed.hip)
-    if ((uint64_t)48 * NE >= (1ull << 32) || (uint64_t)48 * m->num_seg >= (1ull << 32) ||
-        (uint64_t)24 * NE + 8ull * m->num_riv >= (1ull << 32))
-        return 0;
-    {                                                               // 16-bit segment count in the reach index word
-        std::vector<int> cnt(m->num_riv, 0);
-        for (int s = 0; s < m->num_seg; s++)
-            if (++cnt[m->seg_riv[s]] > 0xffff) return 0;
-    }
-    for (int i = 0; i < NE; i++) {
-        if (!(p->aquifer_depth[i] == m->z_surf[i] - m->z_bottom[i])) return 0;
-        const int ibc = m->ibc ? m->ibc[i] : 0;
-        if (ibc > 127 || ibc < -127) return 0;
-        if (seg_off[i + 1] - seg_off[i] > 63) return 0;
-    }
-    // distinct parameter tuples -> class ids
-    std::vector<std::vector<double>> table;           // [class][field]
-    std::vector<int> cls(NE);
-    const double dep_default = 0.0002;
-    auto prim = [&](int i, std::vector<double> &r) {
-        r[CF_macD] = p->macD[i]; r[CF_macKsatH] = p->macKsatH[i]; r[CF_vAreaF] = p->geo_vAreaF[i];
-        r[CF_KsatH] = p->KsatH[i]; r[CF_KsatV] = p->KsatV[i]; r[CF_infKsatV] = p->infKsatV[i];
-        r[CF_hAreaF] = p->hAreaF[i]; r[CF_macKsatV] = p->macKsatV[i]; r[CF_ThetaS] = p->ThetaS[i];
-        r[CF_ThetaR] = p->ThetaR[i]; r[CF_Beta] = p->Beta[i]; r[CF_infD] = p->infD[i]; r[CF_Sy] = p->Sy[i];
-        r[CF_RzD] = p->RzD[i]; r[CF_VegFrac] = p->VegFrac[i]; r[CF_ImpAF] = p->ImpAF[i];
-        r[CF_depression] = m->depression ? m->depression[i] : dep_default;
-        r[CF_rough] = m->rough[i];
-    };
-    // the distinct tuples of the fields outside `mask` (mask fields zeroed), counting stops past `cap`
-    auto count_tuples = [&](uint32_t mask, int cap) {
-        TupleSet seen(CF_NPRIMARY);
-        std::vector<double> r(CF_NPRIMARY);
-        for (int i = 0; i < NE && seen.size() <= cap; i++) {
-            prim(i, r);
-            for (int f = 0; f < CF_NPRIMARY; f++)
-                if (mask >> f & 1) r[f] = 0.;
-            seen.insert(r.data());
-        }
-        return seen.size();
-    };
-    // classes of the fields outside `mask` (mask fields zeroed); false past 32768 classes
-    auto build_classes = [&](uint32_t mask) {
-        table.clear();
-        TupleSet ids(CF_NPRIMARY);
-        std::vector<double> r(CF_NPRIMARY);
-        for (int i = 0; i < NE; i++) {
-            prim(i, r);
-            for (int f = 0; f < CF_NPRIMARY; f++)
-                if (mask >> f & 1) r[f] = 0.;
-            const int id = ids.insert(r.data());
-            if (id == (int)table.size()) {
-                if (id >= 32768) return false;
-                table.push_back(r);
-            }
-            cls[i] = id;
-        }
-        return true;
-    };
-    const bool fits = build_classes(0);
-    // Hybrid layout (per-element-calibrated models): when the full tuples exceed one workgroup's LDS table, stream up
-    // to kHybMax fields per element (8 B each) and keep the rest in the LDS class table — the fields that split the
-    // classes of the non-streamable fields the most first, among those the kernel reads directly (no host-derived
-    // class constant depends on them; Sy's reciprocal is replaced by the IEEE division, the same bits).
-    // SHUD_RHS_HYB=0: off (A/B); =2: KsatH streamed even when the classes fit (timing the hybrid path on any model).
-    uint32_t hmask = 0;
-    const int hyb = env_knob("SHUD_RHS_HYB", 1, 0, 2);
-    if (hyb == 2 && !h->lakeon) {
-        hmask = 1u << CF_KsatH;
-    } else {
-        const uint32_t streamable = 1u << CF_macD | 1u << CF_macKsatH | 1u << CF_vAreaF | 1u << CF_KsatH |
-                                    1u << CF_KsatV | 1u << CF_Sy | 1u << CF_RzD | 1u << CF_depression | 1u << CF_rough;
-        if (!h->lakeon && hyb != 0 && (!fits || (int)table.size() > kLdsClassMax) &&
-            count_tuples(streamable, kLdsClassMax) <= kLdsClassMax) {
-            // base classes: the tuples of the fields that cannot be streamed; then, per streamable field, how many
-            // (base class, value) pairs it makes — the fields that split the base classes most are streamed first
-            TupleSet bid(CF_NPRIMARY);
-            std::vector<int> base(NE);
-            std::vector<double> r(CF_NPRIMARY);
-            for (int i = 0; i < NE; i++) {
-                prim(i, r);
-                for (int f = 0; f < CF_NPRIMARY; f++)
-                    if (streamable >> f & 1) r[f] = 0.;
-                base[i] = bid.insert(r.data());
-            }
-            std::vector<std::pair<size_t, int>> split;       // (distinct (base, value) pairs, field)
-            for (int f = 0; f < CF_NPRIMARY; f++) {
-                if (!(streamable >> f & 1)) continue;
-                TupleSet pairs(2);                           // (base class, field value bits)
-                for (int i = 0; i < NE && pairs.size() <= 1 << 20; i++) {
-                    prim(i, r);
-                    uint64_t key[2];
-                    key[0] = (uint64_t)base[i];
-                    memcpy(&key[1], &r[f], 8);
-                    pairs.insert(key);
-                }
-                if (pairs.size() > bid.size()) split.push_back({(size_t)pairs.size(), f});
-            }
-            std::stable_sort(split.begin(), split.end(),
-                             [](const std::pair<size_t, int> &a, const std::pair<size_t, int> &b) {
-                                 return a.first > b.first;
-                             });
-            for (int k = 0; k < (int)split.size() && k < kHybMax; k++) {
-                hmask |= 1u << split[k].second;
-                if (count_tuples(hmask, kLdsClassMax) <= kLdsClassMax) break;
-                if (k + 1 == kHybMax || k + 1 == (int)split.size()) hmask = 0;   // not enough: no hybrid layout
-            }
-        }
-    }
-    if (hmask) {
-        if (!build_classes(hmask)) return 0;
-    } else if (!fits) {
-        return 0;
-    }
-    const int ncls = (int)table.size();
-    // beyond what a 256-thread workgroup's LDS copy holds (128 classes) the class table goes to 1024-thread
-    // workgroups (up to kLdsClassMaxBig = 600 classes, one per CU); beyond that the lookups would be dependent
-    // L2 trips.  Measured on syn-10M (tools/class_sweep.py, profiles/r02/class_sweep.log): element kernel 0.65 ms
-    // with 33 classes in LDS; from L2 0.83 ms at 132 classes, 1.21 at 495, 1.49 at 1,980, 1.66 at 13,200; the
-    // SoA kernel 1.09 ms at any count -> SoA above 600 (SHUD_RHS_L2_CLASS=1 forces the L2 table at any count and
-    // disables the 1024-thread LDS kernel, =0 forces SoA above 128: A/B and bench.py many_class)
-    const int l2 = env_knob("SHUD_RHS_L2_CLASS", -1, 0, 1);
-    const int l2_max = l2 == 1 ? 32768 : l2 == 0 ? kLdsClassMax : kLdsClassMaxBig;
-    if (ncls > l2_max) return 0;
-    h->dp.lds_big = l2 == 1 ? 0 : 1;
-    std::vector<double> ctab((size_t)CF_STRIDE * ncls, 0.0);
-    for (int c = 0; c < ncls; c++) {
-        std::vector<double> &t = table[c];
-        t.resize(CF_COUNT);
-        // same expressions, same order as the element kernel (-ffp-contract=off on both sides)
-        t[CF_fcmr] = t[CF_ThetaS] * 0.75 - t[CF_ThetaR];
-        t[CF_dTh] = t[CF_ThetaS] - t[CF_ThetaR];
-        t[CF_ex1] = t[CF_Beta] / (t[CF_Beta] - 1.);
-        t[CF_ex2] = (t[CF_Beta] - 1.) / t[CF_Beta];
-        // the packed kernel's satKfun uses pow_tab (positive bases, finite exponents: shud_physics.h);
-        // any other Beta keeps the SoA layout, whose kernel calls the full pow for it
-        if (!(t[CF_Beta] > 1.) || !std::isfinite(t[CF_ex1]) || !std::isfinite(t[CF_ex2])) return 0;
-        t[CF_pj] = 1. - t[CF_ImpAF];
-        t[CF_omh] = 1. - t[CF_hAreaF];
-        t[CF_kmax] = t[CF_infKsatV] * (1. - t[CF_hAreaF]) + t[CF_macKsatV] * t[CF_hAreaF];
-        t[CF_ekA] = t[CF_infKsatV] * (1. - t[CF_hAreaF]);
-        t[CF_ekB] = t[CF_hAreaF] * t[CF_macKsatV];
-        // cdiv's range (shud_dev.h cdiv_divisor_ok); otherwise plain divisions in the SoA kernel
-        if (!cdiv_divisor_ok(t[CF_fcmr]) || !cdiv_divisor_ok(t[CF_dTh]) || !cdiv_divisor_ok(t[CF_infD]) ||
-            !cdiv_divisor_ok(t[CF_Sy]))
-            return 0;
-        t[CF_r_fcmr] = 1. / t[CF_fcmr];
-        t[CF_r_dTh] = 1. / t[CF_dTh];
-        t[CF_r_infD] = 1. / t[CF_infD];
-        t[CF_r_Sy] = 1. / t[CF_Sy];
-        for (int f = 0; f < CF_COUNT; f++)
-            if (cf_stored(f)) ctab[(size_t)c * CF_STRIDE + cf_pos(f)] = t[f];
-    }
-    // pow_tab's tables (shud_pow_tab.h) after the class table, 16-B aligned: one buffer, one LDS copy per workgroup
-    const int pt_off = ((int)ctab.size() + 1) & ~1;
-    ctab.resize((size_t)pt_off + kPowTabDoubles, 0.0);
-#if SHUD_PT_COMPACT
-    static_assert(sizeof shud_pt_clogtab == 8 * kPowTabLogDoubles, "pow_tab");
-    memcpy(&ctab[pt_off], shud_pt_clogtab, sizeof shud_pt_clogtab);
-#else
-    static_assert(kPowTabLogDoubles == 4 * SHUD_PT_LOG_N && sizeof shud_pt_logtab == 8 * kPowTabLogDoubles, "pow_tab");
-    memcpy(&ctab[pt_off], shud_pt_logtab, sizeof shud_pt_logtab);
-#endif
-    static_assert(kPowTabDoubles == kPowTabLogDoubles + 2 * SHUD_PT_EXP_N, "pow_tab table size");
-    memcpy(&ctab[pt_off + kPowTabLogDoubles], shud_pt_exptab, sizeof shud_pt_exptab);
-    std::vector<double2> zz(NE), ged(3 * (size_t)NE);
-    std::vector<int4> meta(NE);
-    std::vector<int> sfirst(NE);
-    for (int i = 0; i < NE; i++) {
-        zz[i] = make_double2(m->z_surf[i], m->z_bottom[i]);
-        const int nseg = seg_off[i + 1] - seg_off[i];
-        const int ibc = (int8_t)(eflags[i] & 0xff);
-        const bool lake_ele = m->ilake && m->ilake[i] > 0 && h->lakeon;
-        const unsigned cf = (unsigned)(ibc & 0xff) | ((unsigned)((eflags[i] >> 16) & 3) << 8) |
-                            ((unsigned)nseg << 10) | ((unsigned)cls[i] << 16) | (lake_ele ? 0x80000000u : 0u);
-        meta[i] = make_int4(m->nabr[i], m->nabr[(size_t)NE + i], m->nabr[2 * (size_t)NE + i], (int)cf);
-        for (int j = 0; j < 3; j++)
-            ged[(size_t)j * NE + i] = make_double2(m->edge[(size_t)j * NE + i], m->dist2nabor[(size_t)j * NE + i]);
-        sfirst[i] = seg_off[i];
-    }
-    // In-tile edge sharing (shud_ele_packed.hip, SH): an interior edge between two elements of one 256-element tile
-    // whose fluxes are exactly antisymmetric (same edge length and Dist2Nabor bits from both sides, same depression,
-    // positive finite avgRough, neither a lake element) is evaluated by one of them and read by the other from LDS.
-    // Greedy in element order: every element publishes at most one edge and receives at most one, never both
-    // directions of one edge.  seg_first bits 26-30 then carry the element's evaluation order (below).
-    // Elements [0, lim): a single-GPU handle's all, a partitioned handle's interior prefix (its ghost-free launch
-    // tiles from element 0), no hybrid layout; the instantiations without sharing that can run on such a handle
-    // (diagnostics, ghosts) evaluate every edge themselves and only decode the order.
-    const int lim = h->n_int > 0 ? h->n_int : (h->n_own == NE ? NE : 0);
-    // Only for handles that take the LSP instantiations (class + pow tables small enough, no lakes, no hybrid
-    // layout): the other instantiations read seg_first with a 31-bit mask (shud_ele_packed.hip ele_body).
-    if (lim > 1 && !hmask && !h->lakeon && lsp_lds_bytes((int)ctab.size()) <= kLspLdsMax && m->num_seg < (1 << 26) &&
-        env_knob("SHUD_RHS_SHARE", 1, 0, 1)) {
-        std::vector<signed char> pub(NE, -1), rcv(NE, -1);
-        auto lake_of = [&](int e) { return m->ilake && m->ilake[e] > 0 && h->lakeon; };
-        for (int i = 0; i < lim; i++) {
-            for (int k = 0; k < 3 && rcv[i] < 0; k++) {
-                const int v = m->nabr[(size_t)k * NE + i];
-                if (v < 0 || v >= lim || v == i || (v / kShareTile) != (i / kShareTile) || pub[v] >= 0) continue;
-                int kk = -1, hits = 0;
-                for (int q = 0; q < 3; q++)
-                    if (m->nabr[(size_t)q * NE + v] == i) { kk = q; hits++; }
-                if (hits != 1 || pub[i] == k) continue;
-                const size_t a = (size_t)k * NE + i, b = (size_t)kk * NE + v;
-                const double ar = m->avg_rough[a];
-                if (memcmp(&m->edge[a], &m->edge[b], 8) || memcmp(&m->dist2nabor[a], &m->dist2nabor[b], 8) ||
-                    (m->depression && memcmp(&m->depression[i], &m->depression[v], 8)) ||   // NULL: 0.0002 everywhere
-                    memcmp(&ar, &m->avg_rough[b], 8) ||
-                    !(ar > 0. && std::isfinite(ar)) || lake_of(i) || lake_of(v))
-                    continue;
-                pub[v] = (signed char)kk;
-                rcv[i] = (signed char)k;
-            }
-        }
-        // The evaluation order (shud_dev.h kEvoShift): first the published slot (else the lowest slot that is not the
-        // received one), last the received slot (else the highest remaining one).  meta's neighbours and the ged planes
-        // are stored in that order, so every pass of the sharing kernel reads one plane, coalesced, with a literal slot;
-        // every other reader (diagnostics, ghost instantiations) goes back through evo_stored().
-        for (int i = 0; i < lim; i++) {
-            const int p = pub[i], r = rcv[i];
-            int e[3];
-            e[0] = p >= 0 ? p : (r == 0 ? 1 : 0);
-            e[2] = r >= 0 ? r : (e[0] == 2 ? 1 : 2);
-            e[1] = 3 - e[0] - e[2];
-            const int nb[3] = {meta[i].x, meta[i].y, meta[i].z};
-            meta[i].x = nb[e[0]]; meta[i].y = nb[e[1]]; meta[i].z = nb[e[2]];
-            for (int s = 0; s < 3; s++)
-                ged[(size_t)s * NE + i] =
-                    make_double2(m->edge[(size_t)e[s] * NE + i], m->dist2nabor[(size_t)e[s] * NE + i]);
-            sfirst[i] |= (int)((evo_encode(e) << kEvoShift) | (p >= 0 ? kEvoPub0 : 0u) | (r >= 0 ? kEvoRcv2 : 0u));
-        }
-        h->n_shared = (int)std::count_if(rcv.begin(), rcv.end(), [](signed char r) { return r >= 0; });
-    }
-    int rc;
-    DevPacked &P = h->dp;
-    double *ctab_d, *area_d; double2 *zz_d, *ged_d; int4 *meta_d; int *sf_d;
-    if ((rc = h->upload(&ctab_d, ctab.data(), ctab.size()))) return rc;
-    if ((rc = h->upload(&zz_d, zz.data(), NE))) return rc;
-    if ((rc = h->upload(&meta_d, meta.data(), NE))) return rc;
-    if ((rc = h->upload(&ged_d, ged.data(), ged.size()))) return rc;
-    if ((rc = h->upload(&area_d, m->area, NE))) return rc;
-    if ((rc = h->upload(&sf_d, sfirst.data(), NE))) return rc;
-    P.ctab = ctab_d; P.ncls = ncls; P.pt_off = pt_off; P.ntab = (int)ctab.size(); P.zz = zz_d;
-    if (hmask) {                                                     // the streamed fields, per element
-        int nh = 0;
-        for (int f = 0; f < CF_NPRIMARY; f++)
-            if (hmask >> f & 1) P.hslot1[f] = (signed char)++nh;
-        const int hs = nh == 1 ? 1 : nh == 2 ? 2 : 4;
-        std::vector<double> hv((size_t)hs * NE, 0.0), rr(CF_NPRIMARY);
-        for (int i = 0; i < NE; i++) {
-            prim(i, rr);
-            for (int f = 0; f < CF_NPRIMARY; f++)
-                if (P.hslot1[f]) hv[(size_t)hs * i + P.hslot1[f] - 1] = rr[f];
-        }
-        double *hv_d;
-        if ((rc = h->upload(&hv_d, hv.data(), hv.size()))) return rc;
-        P.hv = hv_d; P.nh = nh; P.hs = hs;
-        P.hnb = (hmask & (1u << CF_macD | 1u << CF_macKsatH | 1u << CF_vAreaF | 1u << CF_KsatH | 1u << CF_rough)) != 0;
-    } P.meta = meta_d; P.ged = ged_d; P.area = area_d;
-    P.seg_first = sf_d;
-    {   // element-sorted segments {length, Cwr} + their reach; one 32-B record per reach with the statics the segment
-        // fluxes read (seg_perm: element-sorted -> reference)
-        const int NSg = m->num_seg, NRl = m->num_riv;
-        std::vector<double2> lc(NSg), rr(2 * (size_t)NRl);
-        std::vector<int> sr(NSg);
-        for (int k = 0; k < NSg; k++) {
-            const int s = h->seg_perm[k];
-            lc[k] = make_double2(m->seg_length[s], m->seg_cwr[s]);
-            sr[k] = m->seg_riv[s];
-        }
-        for (int r = 0; r < NRl; r++) {
-            const int32_t two[2] = {m->riv_bc ? m->riv_bc[r] : 0, 0};
-            double bits;
-            memcpy(&bits, two, sizeof bits);
-            rr[2 * (size_t)r] = make_double2(m->riv_depth[r], m->riv_ksath[r]);
-            rr[2 * (size_t)r + 1] = make_double2(m->riv_bedthick[r], bits);
-        }
-        double2 *lc_d, *rr_d; int *sr_d;
-        if ((rc = h->upload(&lc_d, lc.data(), NSg))) return rc;
-        if ((rc = h->upload(&sr_d, sr.data(), NSg))) return rc;
-        if ((rc = h->upload(&rr_d, rr.data(), rr.size()))) return rc;
-        P.sg_lc = lc_d; P.sg_r = sr_d; P.rrec = rr_d;
-        if ((rc = h->upload(&P.qseg2, (const double2 *)nullptr, NSg))) return rc;
-    }
-    if ((rc = h->upload(&P.s_np, (const double2 *)nullptr, NE))) return rc;
-    if ((rc = h->upload(&P.s_tl, (const double2 *)nullptr, NE))) return rc;
-    if ((rc = h->upload(&P.cs[0], (const double2 *)nullptr, NE))) return rc;
-    if ((rc = h->upload(&P.cs[1], (const double2 *)nullptr, NE))) return rc;
-    std::vector<double2> ones(NE, make_double2(1.0, 1.0));
-    if ((rc = h->upload(&P.s_fu, ones.data(), NE))) return rc;
-
-    // ---- segments in reach order (stable: reference order inside a reach) and reach records ----
-    const int NS = m->num_seg, NR = m->num_riv;
-    std::vector<int> rorder(NS);
-    std::iota(rorder.begin(), rorder.end(), 0);
-    std::stable_sort(rorder.begin(), rorder.end(), [&](int a, int b) { return m->seg_riv[a] < m->seg_riv[b]; });
-    std::vector<int> rstart(NR, 0), rcnt(NR, 0);
-    for (int q = NS - 1; q >= 0; q--) rstart[m->seg_riv[rorder[q]]] = q;
-    for (int s = 0; s < NS; s++) rcnt[m->seg_riv[s]]++;
-    std::vector<double2> rv(4 * (size_t)NR);
-    std::vector<int4> ru(NR);
-    const int nor = h->n_own_riv;
-    for (int r = 0; r < NR; r++) {
-        const int dn = (h->lakeon && m->riv_down[r] <= -4) ? -3 : m->riv_down[r];   // into a lake: outlet formula
-        const int bc = m->riv_bc ? m->riv_bc[r] : 0;
-        double ib;                                                   // (down, BC) packed into the 4th slot
-        const int32_t two[2] = {dn, bc};
-        memcpy(&ib, two, sizeof ib);
-        rv[4 * (size_t)r + 0] = make_double2(m->riv_bottom_width[r], m->riv_bankslope[r]);
-        rv[4 * (size_t)r + 1] = make_double2(m->riv_length[r], m->riv_bed_slope[r]);
-        rv[4 * (size_t)r + 2] = make_double2(m->riv_dist2down[r], m->riv_avg_rough[r]);
-        rv[4 * (size_t)r + 3] = make_double2(m->riv_depth[r], ib);
-        int4 u = make_int4(rstart[r], rcnt[r], 0, 0);                // rv_u (shud_dev.h); ghosts: segments only
-        if (r < nor) {
-            const int n = up_off[r + 1] - up_off[r];
-            u = n <= 2 ? make_int4(rstart[r], rcnt[r] | (n << 16), n > 0 ? up_idx[up_off[r]] : 0,
-                                   n > 1 ? up_idx[up_off[r] + 1] : 0)
-                       : make_int4(rstart[r], rcnt[r] | (3 << 16), up_off[r], n);
-        }
-        ru[r] = u;
-    }
-    double2 *rv_d; int4 *ru_d;
-    if ((rc = h->upload(&rv_d, rv.data(), rv.size()))) return rc;
-    if ((rc = h->upload(&ru_d, ru.data(), NR))) return rc;
-    P.rv = rv_d; P.rv_u = ru_d;
-    P.riv_sb = choose_riv_sb(rcnt.data(), nor);
-    if (const int sb = env_knob("SHUD_RIV_SB", 0, 6, 8); sb == 6 || sb == 8) P.riv_sb = sb;   // tests: both batch sizes
-    // QrivDown pre-pass slots (shud_dev.h DevPacked::qdown); SHUD_RHS_QD=0: the river kernel recomputes (tests, A/B)
-    if (NR > 0 && env_knob("SHUD_RHS_QD", 1, 0, 1)) {
-        if ((rc = h->upload(&P.qdown, (const double *)nullptr, NR))) return rc;
-        P.nqd = NR;
-    }
-    P.qd_pm = env_knob("SHUD_QD_POS", 1000, 0, 1000);
-    P.qd_pm_fold = env_knob("SHUD_QD_POS_FOLD", 1000, 0, 1000);
-    h->n_classes = ncls;
-    h->packed = true;
-    return 0;
-}
-
-// Lakes: lake / bank-edge / inflow lists in the reference's summation orders, bathymetry.
-static int build_lakes(shud_rhs *h, const ShudMeshSoA *m, const ShudPartition *part) {
-    const int NE = m->num_ele, NR = m->num_riv, NL = h->NL;
-    const int NO = h->n_own;                   // lake and bank elements are owned (partition plan)
-    if (!h->packed)
-        return shud_fail(SHUD_ERR_UNSUPPORTED, "lakes need the packed layout (mesh did not qualify or SHUD_RHS_PACKED=0)");
-    if (h->n_classes > 128) return shud_fail(SHUD_ERR_UNSUPPORTED, "lakes: more than 128 parameter classes");
-    std::vector<int> lake_of(NE, -1), ele_off(NL + 1, 0), bank_off(NL + 1, 0), rin_off(NL + 1, 0);
-    std::vector<int> ele_idx, bank_pos, rin_idx;
-    for (int i = 0; i < NE; i++) {
-        if (m->ilake[i] <= 0) continue;
-        if (i >= NO) return shud_fail(SHUD_ERR_ARG, "lake element %d is a ghost (partition splits a lake group)", i);
-        lake_of[i] = m->ilake[i] - 1;
-        ele_off[m->ilake[i]]++;
-    }
-    // bank edges: a non-lake element's edge whose neighbour is a lake element (lakenabr, MD_Lake.cpp:131-143)
-    auto bank_lake = [&](int i, int j) -> int {
-        if (i >= NO || m->ilake[i] > 0) return -1;
-        const int nb = m->nabr[(size_t)j * NE + i];
-        return (nb >= 0 && m->ilake[nb] > 0) ? m->ilake[nb] - 1 : -1;
-    };
-    for (int i = 0; i < NE; i++)
-        for (int j = 0; j < 3; j++) { const int l = bank_lake(i, j); if (l >= 0) bank_off[l + 1]++; }
-    for (int r = 0; r < NR; r++)
-        if (m->riv_down[r] <= -4) rin_off[(-3 - m->riv_down[r])]++;
-    for (int l = 0; l < NL; l++) {
-        ele_off[l + 1] += ele_off[l]; bank_off[l + 1] += bank_off[l]; rin_off[l + 1] += rin_off[l];
-    }
-    ele_idx.resize(ele_off[NL]); bank_pos.resize(bank_off[NL]); rin_idx.resize(rin_off[NL]);
-    {
-        std::vector<int> fe(ele_off.begin(), ele_off.end() - 1), fb(bank_off.begin(), bank_off.end() - 1),
-            fr(rin_off.begin(), rin_off.end() - 1);
-        for (int i = 0; i < NE; i++) {                  // ascending element, then edge: the reference's order
-            if (m->ilake[i] > 0) ele_idx[fe[m->ilake[i] - 1]++] = i;
-            for (int j = 0; j < 3; j++) { const int l = bank_lake(i, j); if (l >= 0) bank_pos[fb[l]++] = j * NE + i; }
-        }
-        for (int r = 0; r < NR; r++)
-            if (m->riv_down[r] <= -4) { const int l = (-3 - m->riv_down[r]) - 1; rin_idx[fr[l]++] = r; }
-    }
-    // partitioned: local order is [interior | boundary | ghosts] / [owned | ghosts], so put every lake list in
-    // global order (the single-GPU summation order, hence bit-identical sums)
-    if (part && part->ele_gid && part->riv_gid) {
-        const int32_t *eg = part->ele_gid, *rg = part->riv_gid;
-        for (int l = 0; l < NL; l++) {
-            std::sort(ele_idx.begin() + ele_off[l], ele_idx.begin() + ele_off[l + 1],
-                      [&](int a, int b) { return eg[a] < eg[b]; });
-            std::sort(bank_pos.begin() + bank_off[l], bank_pos.begin() + bank_off[l + 1], [&](int a, int b) {
-                const int ia = a % NE, ib = b % NE;                 // pos = j*NE + i: element, then edge
-                return eg[ia] != eg[ib] ? eg[ia] < eg[ib] : a / NE < b / NE;
-            });
-            std::sort(rin_idx.begin() + rin_off[l], rin_idx.begin() + rin_off[l + 1],
-                      [&](int a, int b) { return rg[a] < rg[b]; });
-        }
-    }
-    for (int l = 0; l < NL; l++)
-        if (ele_off[l + 1] == ele_off[l]) return shud_fail(SHUD_ERR_ARG, "lake %d has no lake element", l + 1);
-    DevLake &L = h->lk;
-    L.nl = NL;
-    L.y_off = 3 * h->n_own + h->n_own_riv;    // [sf|us|gw|riv|lake] over owned entities
-    int rc;
-    int *lo, *eo, *ei, *bo, *bp, *ro, *ri, *bto;
-    double *by, *ba;
-    const int nb = m->lake_bathy_off[NL];
-    if ((rc = h->upload(&lo, lake_of.data(), NE)) || (rc = h->upload(&eo, ele_off.data(), NL + 1)) ||
-        (rc = h->upload(&ei, ele_idx.data(), ele_idx.size())) || (rc = h->upload(&bo, bank_off.data(), NL + 1)) ||
-        (rc = h->upload(&bp, bank_pos.data(), bank_pos.size())) || (rc = h->upload(&ro, rin_off.data(), NL + 1)) ||
-        (rc = h->upload(&ri, rin_idx.data(), rin_idx.size())) || (rc = h->upload(&bto, m->lake_bathy_off, NL + 1)) ||
-        (rc = h->upload(&by, m->lake_bathy_y, nb)) || (rc = h->upload(&ba, m->lake_bathy_a, nb)) ||
-        (rc = h->upload(&L.bank_qs, (const double *)nullptr, 3 * (size_t)NE)) ||
-        (rc = h->upload(&L.bank_qg, (const double *)nullptr, 3 * (size_t)NE)))
-        return rc;
-    L.lake_of = lo; L.ele_off = eo; L.ele_idx = ei; L.bank_off = bo; L.bank_pos = bp; L.rin_off = ro; L.rin_idx = ri;
-    L.bathy_off = bto; L.bathy_y = by; L.bathy_a = ba;
-    return 0;
+    if ((rc = h->dalloc(&h->d_y, ny)) || (rc = h->dalloc(&h->d_ydot, ny))) return rc;
+    return h->dalloc(&h->d_scratch_dy, ny);
 }
 
 static int setup_partition(shud_rhs *h, const ShudPartition *part) {

@@ -102,6 +102,10 @@ class ShudPartition(C.Structure):
                 ("ele_gid", c_int32_p), ("riv_gid", c_int32_p), ("nccl_unique_id", C.c_char_p)]
 
 
+class ShudLayoutInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("packed", "n_classes", "n_streamed", "n_shared", "n_int", "riv_sb")]
+
+
 # ---- include/shud_et.h (ET-step prelude) ----
 class ShudEtMeshSoA(C.Structure):
     _fields_ = [("num_ele", C.c_int32), ("iforc", c_int32_p), ("ilc", c_int32_p), ("imf", c_int32_p),
@@ -191,6 +195,8 @@ FUNCTIONS = {
     "shud_rhs_eval_pack": (C.c_int, [_H, C.c_void_p]),
     "shud_rhs_eval_compute": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p]),
     "shud_rhs_debug_halo": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double]),
+    "shud_rhs_plan_layout": (C.c_int, [C.POINTER(ShudMeshSoA), C.POINTER(ShudParamsSoA), C.POINTER(ShudRhsOptions),
+                                       C.POINTER(ShudPartition), C.POINTER(ShudLayoutInfo), c_int32_p, c_int32_p]),
 }
 # include/shud_et.h
 ET_FUNCTIONS = {

@@ -248,6 +248,31 @@ class RhsHandle:
                                          1 if publish else 0, float(timeout_ms)), "debug_halo")
 
 
+def plan_layout(model, mode=abi.SHUD_MODE_SERIAL, partition=None, arrays=False):
+    """What RhsHandle(model, mode, partition=partition) would lay out, derived on the host alone
+    (shud_rhs_plan_layout): the keys of RhsHandle.layout() plus n_int and riv_sb; arrays=True adds edge_plan [NE]
+    (seg_first bits 26-30) and stored_nabr [3, NE] (the neighbours in stored-slot order)."""
+    mesh, par = model.mesh_struct(), model.params_struct()
+    opt = abi.ShudRhsOptions(mode, 0, None, 1)
+    part = None if partition is None else partition.struct()
+    info = abi.ShudLayoutInfo()
+    NE = model.num_ele
+    plan, nabr = (np.zeros(NE, dtype=np.int32), np.zeros((3, NE), dtype=np.int32)) if arrays else (None, None)
+    _check(lib().shud_rhs_plan_layout(C.byref(mesh), C.byref(par), C.byref(opt),
+                                      None if part is None else C.byref(part), C.byref(info),
+                                      None if plan is None else plan.ctypes.data_as(abi.c_int32_p),
+                                      None if nabr is None else nabr.ctypes.data_as(abi.c_int32_p)),
+           "shud_rhs_plan_layout")
+    out = {"packed": bool(info.packed), "n_classes": info.n_classes, "n_int": info.n_int, "riv_sb": info.riv_sb}
+    if info.n_streamed:
+        out["streamed_fields"] = info.n_streamed
+    if info.n_shared:
+        out["shared_edges"] = info.n_shared
+    if arrays:
+        out["edge_plan"], out["stored_nabr"] = plan, nabr
+    return out
+
+
 def nccl_unique_id():
     buf = C.create_string_buffer(128)
     _check(lib().shud_rhs_nccl_unique_id(buf), "nccl_unique_id")

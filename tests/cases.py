@@ -79,6 +79,94 @@ def variant(n=2000, seed=5):
     return m, y
 
 
+# ---- models that take each device layout (the layout tests on the GPU and of the host tables assert which) ----
+def class_count(m):
+    """distinct parameter tuples of a model (the packed layout's classes: shud_tables.cpp class_search)"""
+    keys = ["macD", "macKsatH", "geo_vAreaF", "KsatH", "KsatV", "infKsatV", "hAreaF", "macKsatV", "ThetaS", "ThetaR",
+            "Beta", "infD", "Sy", "RzD", "VegFrac", "ImpAF"]
+    cols = [np.asarray(m.par[k], np.float64) for k in keys] + [np.asarray(m.ele["depression"], np.float64),
+                                                               np.asarray(m.ele["rough"], np.float64)]
+    return np.unique(np.stack(cols, 1), axis=0).shape[0]
+
+
+def many_class_model(sy=True):
+    """per-element calibrated parameters, > 560 distinct tuples: 300 KsatH values and, with `sy`, 7 Sy values (the
+    hybrid layout streams one field without Sy, two with it)"""
+    m, y = variant(20000, seed=17)
+    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 300))
+    if sy:
+        m.par["Sy"] = m.par["Sy"] * (1.0 + 1e-9 * (np.arange(m.num_ele) % 7))
+    return m, y
+
+
+def big_table_model(target="mid"):
+    """-> (model, state, its class count n): 129..560 classes; "max": the most classes still <= 560"""
+    m, y = variant(20000, seed=29)
+    base, k = m.par["KsatH"].copy(), np.arange(m.num_ele)
+    mult, n = 12, 0
+    for mm in ([12] if target == "mid" else range(12, 40)):
+        m.par["KsatH"] = base * (1.0 + 1e-7 * (k % mm))
+        nn = class_count(m)
+        if nn > 560:
+            break
+        mult, n = mm, nn
+    m.par["KsatH"] = base * (1.0 + 1e-7 * (k % mult))
+    assert 128 < n <= 560 and (target == "mid" or n > 520), (mult, n)
+    return m, y, n
+
+
+def mid_class_model():
+    """~66 parameter classes: the LDS class table without the DY-tail LDS slots"""
+    m, y = variant(20000, seed=23)
+    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 2))
+    return m, y
+
+
+def hybrid_model(n=20000, seed=19):
+    """every element its own KsatH, Rough, macD and Sy (four streamed fields, the 32-B per-element record)"""
+    m, y = variant(n, seed=seed)
+    k = np.arange(m.num_ele)
+    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-6 * k / m.num_ele)
+    m.par["macD"] = m.par["macD"] * (1.0 + 1e-3 * ((k * 7) % 11))
+    m.par["Sy"] = m.par["Sy"] * (1.0 + 1e-9 * (k % 13))
+    rough = m.ele["rough"] * (1.0 + 1e-2 * ((k * 3) % 5))
+    m.ele["rough"] = rough
+    nb = m.nabr.reshape(3, -1)          # avgRough = (Rough_i + Rough_j) / 2 (Element.cpp:253), own Rough on a boundary
+    m.ele["avg_rough"] = np.where(nb >= 0, 0.5 * (rough[None, :] + rough[np.maximum(nb, 0)]),
+                                  rough[None, :]).reshape(-1)
+    return m, y
+
+
+def layout_model(kind, monkeypatch):
+    """-> (model, state, check(layout dict)) of one device layout, built as the parity tests build them"""
+    if kind == "packed_share":
+        m, y = variant(3000, seed=5)
+        check = lambda l: l["packed"] and not l.get("streamed_fields") and l.get("shared_edges", 0) > 0  # noqa: E731
+    elif kind == "mid_class":
+        m, y = mid_class_model()
+        check = lambda l: l["packed"] and not l.get("streamed_fields") and 40 <= l["n_classes"] <= 128  # noqa: E731
+    elif kind == "hybrid4":
+        m, y = hybrid_model()
+        check = lambda l: l["packed"] and l.get("streamed_fields") == 4  # noqa: E731
+    elif kind == "big_table":
+        monkeypatch.setenv("SHUD_RHS_HYB", "0")
+        m, y, n = big_table_model("mid")
+        check = lambda l: l["packed"] and not l.get("streamed_fields") and l["n_classes"] == n  # noqa: E731
+    elif kind == "l2":
+        monkeypatch.setenv("SHUD_RHS_HYB", "0")
+        monkeypatch.setenv("SHUD_RHS_L2_CLASS", "1")
+        m, y = many_class_model()
+        n = class_count(m)
+        assert n > 560, n                             # more classes than any LDS table holds
+        check = lambda l: l["packed"] and not l.get("streamed_fields") and l["n_classes"] == n  # noqa: E731
+    else:
+        assert kind == "soa"
+        monkeypatch.setenv("SHUD_RHS_PACKED", "0")
+        m, y = variant(3000, seed=5)
+        check = lambda l: not l["packed"]  # noqa: E731
+    return m, y, check
+
+
 def states(m, y0=None, n_random=4, seed=100):
     out = [] if y0 is None else [y0]
     for k in range(n_random):

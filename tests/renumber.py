@@ -3,8 +3,8 @@
 The C-ABI promises nothing about numbering (include/shud_rhs.h: "reference order"), and the kernels' host tables
 (the in-tile edge-sharing assignment, the element-sorted and reach-sorted segment streams, the junction lists) all
 follow from it.  `renumber` permutes elements, reaches and segments and rotates each element's three edge slots;
-`share_assignment` restates the host's edge-sharing rule (shud_rhs.cpp build_packed) in numpy so that tests can
-state which sharing states an input reaches.
+`share_assignment` and `eval_order` restate the host's edge-sharing rule (shud_tables.cpp share_plan) in numpy, so that
+tests can state which sharing states an input reaches and check the host's plan itself (test_tables.py).
 
 Conventions: new element k is old pe[k], new reach k is old pr[k], new segment k is old ps[k]; new edge slot j of
 new element k is old slot (j + rot[k]) % 3 of old element pe[k].
@@ -224,6 +224,15 @@ def share_assignment(m, lim=None, tile=256):
             pub[v] = kk
             rcv[i] = k
     return pub, rcv
+
+
+def eval_order(pub, rcv):
+    """[3, NE]: the reference slot evaluated first, second and last (the host's rule): first the published slot,
+    else the lowest slot that is not the received one; last the received slot, else the highest remaining one"""
+    pub, rcv = np.asarray(pub, dtype=np.int64), np.asarray(rcv, dtype=np.int64)
+    e0 = np.where(pub >= 0, pub, np.where(rcv == 0, 1, 0))
+    e2 = np.where(rcv >= 0, rcv, np.where(e0 == 2, 1, 2))
+    return np.stack([e0, 3 - e0 - e2, e2])
 
 
 def share_stats(m, pub, rcv, wave=64, tile=256):

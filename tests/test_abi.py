@@ -55,7 +55,8 @@ def test_struct_layouts_match_header():
     for name, cls in [("ShudMeshSoA", abi.ShudMeshSoA), ("ShudParamsSoA", abi.ShudParamsSoA),
                       ("ShudStepInputs", abi.ShudStepInputs), ("ShudRhsOptions", abi.ShudRhsOptions),
                       ("ShudFluxOut", abi.ShudFluxOut), ("ShudErr", abi.ShudErr),
-                      ("ShudPartition", abi.ShudPartition), ("ShudEtMeshSoA", abi.ShudEtMeshSoA),
+                      ("ShudPartition", abi.ShudPartition), ("ShudLayoutInfo", abi.ShudLayoutInfo),
+                      ("ShudEtMeshSoA", abi.ShudEtMeshSoA),
                       ("ShudEtParams", abi.ShudEtParams), ("ShudEtForcing", abi.ShudEtForcing),
                       ("ShudEtOut", abi.ShudEtOut), ("ShudOdeOptions", abi.ShudOdeOptions),
                       ("ShudOdeStats", abi.ShudOdeStats), ("ShudPrintSpec", abi.ShudPrintSpec)]:

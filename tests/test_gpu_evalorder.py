@@ -1,11 +1,11 @@
-"""Edges stored in evaluation order (shud_rhs.cpp build_packed, shud_dev.h kEvoShift; shud_ele_packed.hip SH).
+"""Edges stored in evaluation order (shud_tables.cpp share_plan, shud_dev.h kEvoShift; shud_ele_packed.hip SH).
 
 On a handle that shares edges the host stores every element's three neighbours and {edge, Dist2Nabor} records in the
 order the sharing kernel evaluates them — the published slot first, the received slot last — and the kernels go back
 to the reference's slot order for the sums, the per-slot diagnostics and dist2edge.  Nothing a caller can see may
 change: DY, the error words and every diagnostic array are compared bit for bit with the handle built with
 SHUD_RHS_SHARE=0 (reference order, every edge evaluated from both sides), and DY with the oracle.  The inputs are
-chosen on the CPU (renumber.share_assignment restates the host's pairing, `eval_order` below its ordering rule) so
+chosen on the CPU (renumber.share_assignment restates the host's pairing, renumber.eval_order its ordering rule) so
 that all six orders and all four publish / receive states occur."""
 import functools
 
@@ -15,6 +15,7 @@ import pytest
 import cases
 import renumber as rn
 import test_gpu_partition as tpart
+from renumber import eval_order
 from conftest import assert_close
 from shud_rhs import abi, partition, synth, workload
 
@@ -29,15 +30,6 @@ ORDERS = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
 def _rt():
     from shud_rhs import runtime
     return runtime
-
-
-def eval_order(pub, rcv):
-    """[3, NE]: the reference slot evaluated first, second and last (the host's rule): first the published slot,
-    else the lowest slot that is not the received one; last the received slot, else the highest remaining one"""
-    pub, rcv = np.asarray(pub, dtype=np.int64), np.asarray(rcv, dtype=np.int64)
-    e0 = np.where(pub >= 0, pub, np.where(rcv == 0, 1, 0))
-    e2 = np.where(rcv >= 0, rcv, np.where(e0 == 2, 1, 2))
-    return np.stack([e0, 3 - e0 - e2, e2])
 
 
 @functools.lru_cache(maxsize=None)

@@ -312,10 +312,7 @@ def test_many_classes(oracle_mod, monkeypatch, kind):
     if not kind.startswith("hybrid"):
         monkeypatch.setenv("SHUD_RHS_HYB", "0")
         monkeypatch.setenv("SHUD_RHS_L2_CLASS", "1" if kind == "l2" else "0")
-    m, y = cases.variant(20000, seed=17)
-    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 300))
-    if kind != "hybrid1":                        # hybrid1: KsatH alone (one streamed field, the 8-B record)
-        m.par["Sy"] = m.par["Sy"] * (1.0 + 1e-9 * (np.arange(m.num_ele) % 7))
+    m, y = cases.many_class_model(sy=kind != "hybrid1")   # hybrid1: KsatH alone (one streamed field, the 8-B record)
     if kind.startswith("hybrid"):
         lay = _runtime().RhsHandle(m).layout()
         assert lay["packed"] and lay.get("streamed_fields") == (1 if kind == "hybrid1" else 2), lay
@@ -325,13 +322,7 @@ def test_many_classes(oracle_mod, monkeypatch, kind):
                           label=f"many-class {kind}", layout="soa" if kind == "soa" else "packed")
 
 
-def _class_count(m):
-    """distinct parameter tuples of a model (the packed layout's classes: shud_rhs.cpp build_packed)"""
-    keys = ["macD", "macKsatH", "geo_vAreaF", "KsatH", "KsatV", "infKsatV", "hAreaF", "macKsatV", "ThetaS", "ThetaR",
-            "Beta", "infD", "Sy", "RzD", "VegFrac", "ImpAF"]
-    cols = [np.asarray(m.par[k], np.float64) for k in keys] + [np.asarray(m.ele["depression"], np.float64),
-                                                               np.asarray(m.ele["rough"], np.float64)]
-    return np.unique(np.stack(cols, 1), axis=0).shape[0]
+_class_count = cases.class_count
 
 
 @pytest.mark.parametrize("target", ["mid", "max"])
@@ -341,17 +332,8 @@ def test_lds_big_class_table(oracle_mod, monkeypatch, target):
     "max" sits at the LDS bound (kLdsClassMaxBig = 560 classes: the dynamic-LDS attribute and the 16-B table copy at
     their largest)."""
     monkeypatch.setenv("SHUD_RHS_HYB", "0")
-    m, y = cases.variant(20000, seed=29)
-    base, k = m.par["KsatH"].copy(), np.arange(m.num_ele)
-    mult, n = 12, 0
-    for mm in ([12] if target == "mid" else range(12, 40)):    # "max": the most classes still <= 560
-        m.par["KsatH"] = base * (1.0 + 1e-7 * (k % mm))
-        nn = _class_count(m)
-        if nn > 560:
-            break
-        mult, n = mm, nn
-    m.par["KsatH"] = base * (1.0 + 1e-7 * (k % mult))
-    assert 128 < n <= 560 and (target == "mid" or n > 520), (mult, n)
+    m, y, n = cases.big_table_model(target)
+    assert 128 < n <= 560 and (target == "mid" or n > 520), n
     lay = _runtime().RhsHandle(m).layout()
     assert lay["packed"] and not lay.get("streamed_fields") and lay["n_classes"] == n, lay
     for mode in (abi.SHUD_MODE_SERIAL, abi.SHUD_MODE_OMP):
@@ -363,27 +345,14 @@ def test_lds_big_class_table(oracle_mod, monkeypatch, target):
 def test_mid_class_count(mode, oracle_mod):
     """~66 parameter classes: the LDS class table without the DY-tail LDS slots (they fit beside tables of up to
     ~35 classes only, shud_ele_packed.hip LSP), against the oracle."""
-    m, y = cases.variant(20000, seed=23)
-    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 2))
+    m, y = cases.mid_class_model()
     lay = _runtime().RhsHandle(m, mode=mode).layout()
     assert lay["packed"] and not lay.get("streamed_fields") and 40 <= lay["n_classes"] <= 128, lay
     _compare_sequence(m, [y] + cases.states(m, None, 1, seed=5), mode, oracle_mod, ncalls=2, label="mid-class",
                       layout="packed")
 
 
-def _hybrid_model(n=20000, seed=19):
-    """every element its own KsatH, Rough, macD and Sy (four streamed fields, the 32-B per-element record)"""
-    m, y = cases.variant(n, seed=seed)
-    k = np.arange(m.num_ele)
-    m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-6 * k / m.num_ele)
-    m.par["macD"] = m.par["macD"] * (1.0 + 1e-3 * ((k * 7) % 11))
-    m.par["Sy"] = m.par["Sy"] * (1.0 + 1e-9 * (k % 13))
-    rough = m.ele["rough"] * (1.0 + 1e-2 * ((k * 3) % 5))
-    m.ele["rough"] = rough
-    nb = m.nabr.reshape(3, -1)          # avgRough = (Rough_i + Rough_j) / 2 (Element.cpp:253), own Rough on a boundary
-    m.ele["avg_rough"] = np.where(nb >= 0, 0.5 * (rough[None, :] + rough[np.maximum(nb, 0)]),
-                                  rough[None, :]).reshape(-1)
-    return m, y
+_hybrid_model = cases.hybrid_model
 
 
 @pytest.mark.parametrize("mode", [abi.SHUD_MODE_SERIAL, abi.SHUD_MODE_OMP])

@@ -32,41 +32,7 @@ OMP_SKIPPED = ("q_es", "q_eu", "q_eg", "q_tu", "q_tg", "q_eta", "i_beta")       
 
 
 # ---------------------------------------------------------------- a. numbering invariance, bit for bit
-def _layout_model(kind, monkeypatch):
-    """-> (model, state, check(layout dict)) of one device layout, built as the parity tests build them"""
-    if kind == "packed_share":
-        m, y = cases.variant(3000, seed=5)
-        check = lambda l: l["packed"] and not l.get("streamed_fields") and l.get("shared_edges", 0) > 0  # noqa: E731
-    elif kind == "mid_class":
-        m, y = cases.variant(20000, seed=23)
-        m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 2))
-        check = lambda l: l["packed"] and not l.get("streamed_fields") and 40 <= l["n_classes"] <= 128  # noqa: E731
-    elif kind == "hybrid4":
-        m, y = tp._hybrid_model()
-        check = lambda l: l["packed"] and l.get("streamed_fields") == 4  # noqa: E731
-    elif kind == "big_table":
-        monkeypatch.setenv("SHUD_RHS_HYB", "0")
-        m, y = cases.variant(20000, seed=29)
-        m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (np.arange(m.num_ele) % 12))
-        n = tp._class_count(m)
-        assert 128 < n <= 560, n
-        check = lambda l: l["packed"] and not l.get("streamed_fields") and l["n_classes"] == n  # noqa: E731
-    elif kind == "l2":
-        monkeypatch.setenv("SHUD_RHS_HYB", "0")
-        monkeypatch.setenv("SHUD_RHS_L2_CLASS", "1")
-        m, y = cases.variant(20000, seed=17)
-        k = np.arange(m.num_ele)
-        m.par["KsatH"] = m.par["KsatH"] * (1.0 + 1e-7 * (k % 300))
-        m.par["Sy"] = m.par["Sy"] * (1.0 + 1e-9 * (k % 7))
-        n = tp._class_count(m)
-        assert n > 560, n                             # more classes than any LDS table holds
-        check = lambda l: l["packed"] and not l.get("streamed_fields") and l["n_classes"] == n  # noqa: E731
-    else:
-        assert kind == "soa"
-        monkeypatch.setenv("SHUD_RHS_PACKED", "0")
-        m, y = cases.variant(3000, seed=5)
-        check = lambda l: not l["packed"]  # noqa: E731
-    return m, y, check
+_layout_model = cases.layout_model
 
 
 def _gpu_sequence(m, ys, mode, check, ncalls=2):
@@ -75,6 +41,8 @@ def _gpu_sequence(m, ys, mode, check, ncalls=2):
     try:
         lay = g.layout()
         assert check(lay), lay
+        plan = tp._runtime().plan_layout(m, mode=mode)      # the host tables alone say the same
+        assert {k: v for k, v in plan.items() if k not in ("n_int", "riv_sb")} == lay, (plan, lay)
         g.set_step_inputs()
         seq = [g.eval(0.0, y) for y in ys for _ in range(ncalls)]       # raises on an error exit
         return seq, g.diagnostics(), lay

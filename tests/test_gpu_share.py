@@ -1,4 +1,4 @@
-"""In-tile edge sharing (shud_ele_packed.hip SH, the host's assignment in shud_rhs.cpp build_packed): an interior edge
+"""In-tile edge sharing (shud_ele_packed.hip SH, the host's assignment in shud_tables.cpp share_plan): an interior edge
 evaluated by one element and read, sign-corrected, by the other must leave every DY word and every error word exactly
 as evaluating the edge from both sides does (SHUD_RHS_SHARE=0), and agree with the oracle.  The states aim at the
 sign rules: equal surface / groundwater heads across edges (dh == +0, dhg == +0: no negation), dry cells (no Manning),

@@ -1,7 +1,7 @@
 """Element-kernel time vs number of parameter classes on syn-10M (KsatH perturbed by element mod M, 33 x M
 classes): the default dispatch (LDS class table: 256-thread workgroups up to 128 classes, 1024-thread workgroups
 up to 600, SoA above), the packed layout with the class table read from L2 (SHUD_RHS_L2_CLASS=1) and the SoA
-layout, to place the layout switches (shud_rhs.cpp build_packed).  Prints one line per (M, path)."""
+layout, to place the layout switches (shud_tables.cpp class_table).  Prints one line per (M, path)."""
 import copy
 import os
 import sys
