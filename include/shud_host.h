@@ -76,6 +76,9 @@ int shud_project_et(shud_project_t p, ShudEtMeshSoA *mesh, ShudEtParams *par);
 const double *shud_project_array(shud_project_t p, const char *name, int64_t *n);
 /* print controls for output directory `outdir` (created by the caller); returns the count, fills up to max */
 int shud_project_outputs(shud_project_t p, const char *outdir, ShudOutputDecl *decl, int max);
+/* output interval [min] of the water-balance diagnostics (include/shud_wb.h): dt_qe_ET if positive, else
+ * dt_ye_SURF if positive, else 1440 (choose_interval_min, src/Model/WaterBalanceDiag.cpp:10-19); -1 for NULL */
+int shud_project_wb_interval(shud_project_t p);
 
 /* Per ET step [t, tout): updateAllTimeSeries(t) (movePointer of every forcing / LAI / MF series) and the
  * inputs of tReadForcing + ET for shud_et_step: the current station rows, LAI and MF rows, and the TSR

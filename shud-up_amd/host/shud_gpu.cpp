@@ -16,8 +16,14 @@
 //        updateAllTimeSeries(t); updateforcing(t); ET(t, tout)   -> shud_project_forcing + shud_et_step
 //        [CVodeSetStopTime(tout)]; CVode(mem, tout, udata, &t, CV_NORMAL)  -> shud_ode_solve (y in HBM)
 //     summary(udata); ExportResults(t)   -> shud_rhs_summary + shud_rhs_refresh_diagnostics + shud_out_export
-// Not restated (out of the device path's scope): water-balance diagnostics (SHUD_WB_DIAG), flood alerts,
-// the screen print / .cfg.ic.update snapshots, NetCDF forcing and outputs, the uncoupled -g mode.
+// With SHUD_WB_DIAG set (env_truthy, WaterBalanceDiag.cpp:21-36, after shud.cpp:72's test) the water-balance
+// diagnostics of shud.cpp:70-75,110-112,137-152 run on the device (include/shud_wb.h): onETUpdate after every ET
+// step; after summary the extra, stateful f() on the accepted state, CVodeGetDky(k = 1), sample and maybeWrite,
+// then ExportResults.  SHUD_WB_DIAG_TRAPZ selects the trapezoid rule; SHUD_WB_DIAG_QUAD is not supported (one line
+// says so).  Without SHUD_WB_DIAG the loop makes exactly the calls it made before.
+// Not restated (out of the device path's scope): flood alerts, the screen print / .cfg.ic.update snapshots,
+// NetCDF forcing and outputs, the uncoupled -g mode.
+#include <strings.h>
 #include <sys/stat.h>
 
 #include <chrono>
@@ -33,6 +39,7 @@
 #include "shud_ode.h"
 #include "shud_out.h"
 #include "shud_rhs.h"
+#include "shud_wb.h"
 
 static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 
@@ -54,6 +61,15 @@ static int mkdirs(const std::string &d) {
     }
     struct stat st;
     return stat(d.c_str(), &st) == 0 ? 0 : -1;
+}
+
+// env_truthy (WaterBalanceDiag.cpp:21-36): unset, "", "0", "false" and "off" (any case) are false
+static bool env_truthy(const char *s) {
+    if (s == nullptr || s[0] == '\0') return false;
+    if (strcmp(s, "0") == 0) return false;
+    if (strcasecmp(s, "false") == 0) return false;
+    if (strcasecmp(s, "off") == 0) return false;
+    return true;
 }
 
 static const char *lonlat_name(int m) { return m == 1 ? "FORCING_MEAN" : (m == 2 ? "FIXED" : "FORCING_FIRST"); }
@@ -178,6 +194,24 @@ int main(int argc, char **argv) {
         nprint++;
     }
 
+    // ---- WaterBalanceDiag::enable (shud.cpp:70-75): shud.cpp:72's test, then openFiles' env_truthy ----
+    shud_wb_t wb = nullptr;
+    double *d_du = nullptr;
+    const char *wb_env = getenv("SHUD_WB_DIAG");
+    if (wb_env != nullptr && wb_env[0] != '\0' && strcmp(wb_env, "0") != 0 && env_truthy(wb_env)) {
+        if (env_truthy(getenv("SHUD_WB_DIAG_QUAD")))
+            fprintf(stderr, "shud_gpu: SHUD_WB_DIAG_QUAD is not supported; running without the CV_ONE_STEP monitor\n");
+        const std::string prefix = outdir + "/" + prj;
+        ShudWbOptions wo = {c.start_time, shud_project_wb_interval(p), env_truthy(getenv("SHUD_WB_DIAG_TRAPZ")) ? 1 : 0,
+                            (int64_t)c.forc_start_time, c.radiation_input_mode, c.terrain_radiation,
+                            lonlat_name(c.solar_lonlat_mode), c.solar_lon_deg, c.solar_lat_deg, prefix.c_str()};
+        if (shud_wb_create(h, &mesh, &par, &wo, &wb) ||
+            shud_rhs_device_alloc(h, (size_t)ny * sizeof(double), (void **)&d_du)) {
+            fprintf(stderr, "shud_wb_create: %s\n", shud_rhs_last_error_string());
+            return 1;
+        }
+    }
+
     // ---- the time loop (shud.cpp:86-140) ----
     shud_rhs_synchronize(h);
     const auto loop0 = std::chrono::steady_clock::now();
@@ -186,7 +220,7 @@ int main(int argc, char **argv) {
     const long long nsteps = max_steps >= 0 && max_steps < c.num_steps ? max_steps : c.num_steps;
     int rc = 0;
     // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
-    double ph[5] = {0, 0, 0, 0, 0};         // forcing+BC rows, ET step, CVode, summary+diagnostics, export
+    double ph[6] = {0, 0, 0, 0, 0, 0};      // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag
     auto tick = std::chrono::steady_clock::now();
     auto lap = [&](int k) {
         const auto now = std::chrono::steady_clock::now();
@@ -218,6 +252,14 @@ int main(int argc, char **argv) {
                 break;
             }
             lap(1);
+            if (wb) {                               // wbdiag->onETUpdate()
+                if (shud_wb_on_et_update(wb)) {
+                    fprintf(stderr, "shud_wb_on_et_update: %s\n", shud_rhs_last_error_string());
+                    rc = 1;
+                    break;
+                }
+                lap(5);
+            }
             if (et_sub) shud_ode_set_stop_time(ode, tout);
             const int flag = shud_ode_solve(ode, tout, d_y, SHUD_WHERE_DEVICE, &t, SHUD_ODE_NORMAL);
             if (flag < 0) {
@@ -237,8 +279,24 @@ int main(int argc, char **argv) {
         }
         if (rc) break;
         shud_rhs_summary(h, d_y);                 // Model_Data::summary(udata)
-        shud_rhs_refresh_diagnostics(h);          // the flux arrays of CVODE's last f() call
-        lap(3);
+        if (wb) {
+            lap(3);
+            // f(t, udata, du, MD) on the accepted state (stateful: advances qEleE_IC and the carried u_satn, as in
+            // the reference), its flux arrays, CVodeGetDky(mem, t, 1, du), sample(t, du), maybeWrite(t)
+            int wrc = shud_rhs_eval(h, t, d_y, d_du, SHUD_WHERE_DEVICE);
+            if (!wrc) wrc = shud_rhs_refresh_diagnostics(h);
+            if (!wrc) wrc = shud_ode_get_dky(ode, t, 1, d_du, SHUD_WHERE_DEVICE);
+            if (!wrc) wrc = shud_wb_sample(wb, t, d_du);
+            if (!wrc && shud_wb_maybe_write(wb, t) < 0) wrc = 1;
+            if (wrc) {
+                fprintf(stderr, "water-balance diagnostics: %s (code %d)\n", shud_rhs_last_error_string(), wrc);
+                rc = 1;
+            }
+            lap(5);
+        } else {
+            shud_rhs_refresh_diagnostics(h);      // the flux arrays of CVODE's last f() call
+            lap(3);
+        }
         if (shud_out_export(out, t)) {            // Control_Data::ExportResults(t)
             fprintf(stderr, "shud_out_export: %s\n", shud_rhs_last_error_string());
             rc = 1;
@@ -249,6 +307,10 @@ int main(int argc, char **argv) {
     shud_rhs_synchronize(h);
     const double loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop0).count();
     shud_out_destroy(out);
+    if (wb && shud_wb_destroy(wb)) {
+        fprintf(stderr, "shud_wb_destroy: %s\n", shud_rhs_last_error_string());
+        if (!rc) rc = 1;
+    }
     ShudOdeStats st;
     shud_ode_get_stats(ode, &st);
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
@@ -261,11 +323,13 @@ int main(int argc, char **argv) {
     printf("{\"shud_gpu\": {\"num_ele\": %d, \"t_end_min\": %.6f, \"solver_steps\": %lld, \"cvode_steps\": %lld, "
            "\"rhs_evals\": %lld, \"newton_iters\": %lld, \"krylov_iters\": %lld, \"outputs\": %d, "
            "\"wall_s\": %.4f, \"loop_s\": %.4f, \"loop_phases_s\": {\"forcing\": %.4f, \"et_step\": %.4f, "
-           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f}, \"host_syncs\": %lld, \"exit\": %d}}\n",
+           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f}, \"host_syncs\": %lld, "
+           "\"exit\": %d}}\n",
            mesh.num_ele, t, nsteps, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni,
-           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], (long long)st.n_sync, rc);
+           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], (long long)st.n_sync, rc);
     shud_ode_destroy(ode);
     shud_rhs_device_free(h, d_y);
+    if (d_du) shud_rhs_device_free(h, d_du);
     shud_rhs_destroy(h);
     shud_project_free(p);
     return rc;

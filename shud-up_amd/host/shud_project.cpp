@@ -561,6 +561,15 @@ int shud_project_control(shud_project_t h, ShudControl *c) {
     return 0;
 }
 
+// choose_interval_min (WaterBalanceDiag.cpp:10-19)
+int shud_project_wb_interval(shud_project_t h) {
+    if (!h) return -1;
+    const Project &p = *reinterpret_cast<Project *>(h);
+    if (p.dt_qe_et > 0) return p.dt_qe_et;
+    if (p.dt_ye_surf > 0) return p.dt_ye_surf;
+    return 1440;
+}
+
 int shud_project_mesh(shud_project_t h, ShudMeshSoA *m, ShudParamsSoA *q) {
     if (!h || !m || !q) return fail(nullptr, "null argument");
     Project &p = *reinterpret_cast<Project *>(h);

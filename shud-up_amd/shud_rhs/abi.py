@@ -249,11 +249,43 @@ OUT_FUNCTIONS = {
     "shud_out_destroy": (C.c_int, [_H]),
 }
 
+# ---- include/shud_wb.h (water-balance diagnostics on the device) ----
+(SHUD_WB_P, SHUD_WB_ET, SHUD_WB_QOUT, SHUD_WB_QEDGE, SHUD_WB_QBC, SHUD_WB_QSS, SHUD_WB_NONCONS, SHUD_WB_NBASIN) = range(8)
+SHUD_WB_ERR_IO = -6
+WB_ARRAYS = ["acc3", "accfull", "acc3_budget", "accfull_budget", "resid3", "residfull", "resid3_budget",
+             "residfull_budget"]
+
+
+class ShudWbOptions(C.Structure):
+    _fields_ = [("start_time", C.c_double), ("interval_min", C.c_int32), ("trapz", C.c_int32),
+                ("forc_start_time", C.c_int64), ("radiation_input_mode", C.c_int32), ("terrain_radiation", C.c_int32),
+                ("solar_lonlat_mode", C.c_char_p), ("solar_lon_deg", C.c_double), ("solar_lat_deg", C.c_double),
+                ("prefix", C.c_char_p)]
+
+
+class ShudWbOut(C.Structure):
+    _fields_ = [(n, c_double_p) for n in WB_ARRAYS] + [
+        ("basin_acc", C.c_double * SHUD_WB_NBASIN), ("basin_rate", C.c_double * SHUD_WB_NBASIN),
+        ("basin_row", C.c_double * 9), ("storage", C.c_double * 2), ("last_t", C.c_double), ("rows", C.c_int64),
+        ("n_outlets", C.c_int32)]
+
+
+WB_FUNCTIONS = {
+    "shud_wb_create": (C.c_int, [_H, C.POINTER(ShudMeshSoA), C.POINTER(ShudParamsSoA), C.POINTER(ShudWbOptions),
+                                 C.POINTER(_H)]),
+    "shud_wb_on_et_update": (C.c_int, [_H]),
+    "shud_wb_sample": (C.c_int, [_H, C.c_double, C.c_void_p]),
+    "shud_wb_maybe_write": (C.c_int, [_H, C.c_double]),
+    "shud_wb_read": (C.c_int, [_H, C.POINTER(ShudWbOut)]),
+    "shud_wb_destroy": (C.c_int, [_H]),
+    "shud_wb_time_samples": (C.c_int, [_H, C.c_void_p, C.c_int, c_double_p]),
+}
+
 
 def bind(lib, strict=True):
     """set the signatures; strict=False (A/B builds of older sources) skips symbols the library lacks"""
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
-                              + list(OUT_FUNCTIONS.items())):
+                              + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

@@ -54,6 +54,7 @@ def lib():
             "shud_project_et": (C.c_int, [_H, C.POINTER(abi.ShudEtMeshSoA), C.POINTER(abi.ShudEtParams)]),
             "shud_project_array": (C.POINTER(C.c_double), [_H, C.c_char_p, C.POINTER(C.c_int64)]),
             "shud_project_outputs": (C.c_int, [_H, C.c_char_p, C.POINTER(ShudOutputDecl), C.c_int]),
+            "shud_project_wb_interval": (C.c_int, [_H]),
             "shud_project_forcing": (C.c_int, [_H, C.c_double, C.c_double, C.POINTER(abi.ShudEtForcing)]),
             "shud_project_bc_rows": (C.c_int, [_H, C.POINTER(abi.ShudStepInputs)]),
             "shud_project_solar": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -150,6 +151,10 @@ class Project:
         return [{"basename": d.basename.decode(), "array": d.array, "column": d.column, "n_all": d.n_all,
                  "interval": d.interval, "iflux": d.iflux,
                  "flag_io": None if not d.flag_io else _arr(d.flag_io, d.n_all, np.int32)} for d in arr[:n]]
+
+    def wb_interval(self):
+        """output interval [min] of the water-balance diagnostics: dt_qe_ET, else dt_ye_SURF, else 1440"""
+        return lib().shud_project_wb_interval(self.h)
 
     def bc_rows(self):
         """{ele_ybc, ele_qbc, riv_ybc, riv_qbc} rows at the current ET step (model.step_struct bc_tables form:

@@ -324,6 +324,12 @@ class OdeSolver:
         flag = lib().shud_ode_get_dky(self.h, float(t), int(k), d.ctypes.data, abi.SHUD_WHERE_HOST)
         return flag, d
 
+    def get_dky_device(self, t, k, d_out):
+        """CVodeGetDky(mem, t, k, dky) into device memory at d_out (NY doubles)"""
+        flag = lib().shud_ode_get_dky(self.h, float(t), int(k), C.c_void_p(d_out), abi.SHUD_WHERE_DEVICE)
+        if flag != abi.ODE_SUCCESS:
+            raise RuntimeError(f"shud_ode_get_dky failed with flag {flag}")
+
     def stats(self):
         s = abi.ShudOdeStats()
         lib().shud_ode_get_stats(self.h, C.byref(s))
@@ -382,6 +388,71 @@ class Output:
             rc = lib().shud_out_destroy(self.h)
             self.h = None
             _check(rc, "shud_out_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class WaterBalance:
+    """The reference's WaterBalanceDiag (SHUD_WB_DIAG) on the device (include/shud_wb.h) over a serial RhsHandle:
+    on_et_update() = onETUpdate, sample(t, d_dy) = sample, maybe_write(t) = maybeWrite.  Construct after
+    handle.summary(y0).  prefix: <outdir>/<prj>, the five .dat files; None = no files, read() only."""
+
+    def __init__(self, handle, interval, start_time=0.0, trapz=False, prefix=None, forc_start_time=0,
+                 radiation_input_mode=0, terrain_radiation=0, solar_lonlat_mode="FORCING_FIRST", lon=0.0, lat=0.0):
+        self._rhs = handle
+        self.num_ele = handle.model.num_ele
+        self._keep = (None if prefix is None else str(prefix).encode(), str(solar_lonlat_mode).encode())
+        opt = abi.ShudWbOptions(float(start_time), int(interval), int(bool(trapz)), int(forc_start_time),
+                                int(radiation_input_mode), int(terrain_radiation), self._keep[1], float(lon),
+                                float(lat), self._keep[0])
+        h = C.c_void_p()
+        _check(lib().shud_wb_create(handle.h, C.byref(handle._mesh), C.byref(handle._par), C.byref(opt), C.byref(h)),
+               "shud_wb_create")
+        self.h = h
+
+    def on_et_update(self):
+        _check(lib().shud_wb_on_et_update(self.h), "shud_wb_on_et_update")
+
+    def sample(self, t, d_dy):
+        _check(lib().shud_wb_sample(self.h, float(t), C.c_void_p(d_dy)), "shud_wb_sample")
+
+    def maybe_write(self, t):
+        """True when a row was written"""
+        rc = lib().shud_wb_maybe_write(self.h, float(t))
+        if rc < 0:
+            _check(rc, "shud_wb_maybe_write")
+        return rc == 1
+
+    def read(self, arrays=True):
+        """dict of host copies: the four accumulators, the residuals of the last written row (arrays=True), the
+        basin accumulators / rates / last row, the two storages, last_t, rows, n_outlets"""
+        o = abi.ShudWbOut()
+        out = {}
+        if arrays:
+            for name in abi.WB_ARRAYS:
+                out[name] = np.zeros(self.num_ele)
+                setattr(o, name, out[name].ctypes.data_as(abi.c_double_p))
+        _check(lib().shud_wb_read(self.h, C.byref(o)), "shud_wb_read")
+        out.update(basin_acc=np.array(o.basin_acc), basin_rate=np.array(o.basin_rate), basin_row=np.array(o.basin_row),
+                   storage=np.array(o.storage), last_t=o.last_t, rows=o.rows, n_outlets=o.n_outlets)
+        return out
+
+    def time_samples(self, d_dy, reps):
+        """milliseconds per sample pass over `reps` passes (HIP events; shud_wb_time_samples)"""
+        ms = C.c_double()
+        _check(lib().shud_wb_time_samples(self.h, C.c_void_p(d_dy), int(reps), C.byref(ms)), "shud_wb_time_samples")
+        return ms.value
+
+    def close(self):
+        """shud_wb_destroy; raises on a write error.  Call before the handle's close()."""
+        if self.h:
+            rc = lib().shud_wb_destroy(self.h)
+            self.h = None
+            _check(rc, "shud_wb_destroy")
 
     def __del__(self):
         try:

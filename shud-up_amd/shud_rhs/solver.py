@@ -50,15 +50,24 @@ class ShudSolver:
                              ctl.min_step, ctl.max_num_steps)
         self.y = None
 
-    def run(self, num_steps, forcing=None, on_output=None, output=None):
+    def run(self, num_steps, forcing=None, on_output=None, output=None, wb=None):
         """num_steps solver steps (the reference's NumSteps loop); on_output(i, t, y) after each (host copy of y).
         output: runtime.Output whose controls point at the handle's device arrays — after each solver step
-        summary(udata) + ExportResults(t) run on the device (shud.cpp:137,153): no host copy of y at all."""
+        summary(udata) + ExportResults(t) run on the device (shud.cpp:137,153): no host copy of y at all.
+        wb: runtime.WaterBalance (needs output) — the reference's SHUD_WB_DIAG hooks (shud.cpp:110-112,137-152):
+        onETUpdate after every ET step; after summary the extra, stateful f() on the accepted state, CVodeGetDky(k = 1),
+        sample and maybeWrite, then ExportResults.  The extra f() advances the carried state: the trajectory differs
+        from a run without wb, as in the reference."""
         ctl = self.ctl
         tnext = self.t
         d_y = None
+        if wb is not None and output is None:
+            raise ValueError("wb needs output (the device-resident loop)")
         if output is not None:
             d_y = self._out_y = getattr(self, "_out_y", None) or self.h.device_alloc(8 * self.h.num_y)
+        d_du = None
+        if wb is not None:
+            d_du = self._wb_du = getattr(self, "_wb_du", None) or self.h.device_alloc(8 * self.h.num_y)
         for i in range(num_steps):
             tnext += ctl.solver_step
             while self.t + ZERO < tnext:
@@ -67,6 +76,8 @@ class ShudSolver:
                     f = forcing(self.t, tout)
                     if f is not None:
                         self.h.et_step(f)
+                if wb is not None:
+                    wb.on_et_update()
                 if ctl.et_substep:
                     self.ode.set_stop_time(tout)
                 if d_y is not None:
@@ -86,7 +97,13 @@ class ShudSolver:
                 # replayed on its input buffer (the integrator never rewrites that buffer before its next RHS
                 # call: the Newton residual's y and the DQ work vector are only written right before an RHS)
                 self.h.summary(d_y)
+                if wb is not None:
+                    self.h.eval_device(self.t, d_y, d_du)
                 self.h.refresh_diagnostics()
+                if wb is not None:
+                    self.ode.get_dky_device(self.t, 1, d_du)
+                    wb.sample(self.t, d_du)
+                    wb.maybe_write(self.t)
                 output.export(self.t)
             if on_output is not None:
                 if self.y is None:
@@ -99,6 +116,7 @@ class ShudSolver:
 
     def close(self):
         self.ode.close()
-        if getattr(self, "_out_y", None):
-            self.h.device_free(self._out_y)
-            self._out_y = None
+        for name in ("_out_y", "_wb_du"):
+            if getattr(self, name, None):
+                self.h.device_free(getattr(self, name))
+                setattr(self, name, None)
