@@ -118,6 +118,21 @@ static_assert(2 * kEleBS * 8 + kEleBS <= kPowTabDoubles * 8, "edge-sharing slots
 // gathering the one out-of-tile neighbour before the loop took 94 VGPRs and was slower, profiles/r05/nb_lds/.  Two tiles
 // per workgroup sharing one table copy: 83 VGPRs / 5 waves 0.628 ms, forced to 6 waves 0.606 vs 0.602 ms,
 // profiles/r05/tiles2/.  Round-5 A/B switches that measured slower were removed in round 6; commit a4b4e96 holds them.)
+// the loads of one river segment (ele_body seg_a, seg_b): its reach index and {length, Cwr}, then the reach's
+// {depth, KsatH | BedThick, BC} record and the reach's stage in y
+struct SegIn {
+    int rr;
+    double2 lc, dk, rx;
+    double yr;
+};
+// the loads of one stored edge slot (ele_body edge_load): the neighbour (-1: boundary), the slot's {edge length,
+// Dist2Nabor}, and the neighbour's {z_surf, z_bottom}, cf word, surface and groundwater states
+struct EdgeIn {
+    int nb;
+    double2 g, nzz;
+    int ncf;
+    double nsf_raw, ngw_raw;
+};
 // the element's own records, loaded before the workgroup's class-table barrier so both round trips overlap
 struct OwnRec {
     int4 mt;
@@ -372,7 +387,9 @@ __device__ __forceinline__ void hload(const DevPacked &p, int i, double (&v)[4])
 
 // (Edge j+1's neighbour gathers issued at the top of edge j's iteration, or edge 0's before the segment loop: 92 / 94
 // VGPRs, 5 waves per SIMD, element kernel 0.620 / 0.627 vs 0.600 ms; forced to 6 waves it spills (0.752).  Occupancy
-// hides the gathers' latency better than the extra loads in flight per wave, profiles/r05/edge_pf/.)
+// hides the gathers' latency better than the extra loads in flight per wave, profiles/r05/edge_pf/.  Round 8 moves
+// loads only to points where the registers are free: the first segment's under the vertical physics, the two
+// straight-line edge stages' ahead of the barrier in front of each, profiles/r08/loadorder/.)
 template <int MODE, bool OPEN, bool DIAG, bool FU1, bool LCT, bool LAKE, bool GH, int HYB, int LSP, int BS>
 __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, const YView &Y, double *__restrict__ dy,
                                          int i, int cur, const DevDiag &dg, const DevLake &lk, const double *lct,
@@ -441,6 +458,28 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
     const int sfirst = sfl & ((LSP || DIAG || !LCT) ? 0x03ffffff : 0x7fffffff);
     const bool lai_on = sfl < 0;                       // bit 31: t_lai > ZERO (set with the step inputs)
     const int iss = cf_iss(cf), nseg = cf_nseg(cf);
+    // a segment's loads in their two dependent steps (the segment section below).  The first segment's are issued
+    // under the vertical physics, by the lanes that own a segment (a riverless model has no segment arrays at all):
+    // seg_a behind the carried-state store, seg_b behind the LDS parking — the earliest points that keep the sharing
+    // instantiations at 72 VGPRs without scratch (seg_a behind satKfun, or seg_b ahead of infiltration / recharge:
+    // 20-52 B of scratch per lane in the serial-mode ones, profiles/r08/loadorder/).
+    // (Round 3 held the reach index + stage from the top of the body: 88 VGPRs, 0.625 vs 0.623 ms,
+    // profiles/r03/ab_river2/)
+    auto seg_a = [&](int k, SegIn &si) __attribute__((always_inline)) {
+        si.rr = *at(p.sg_r, (uint32_t)k << 2);
+        si.lc = *at(p.sg_lc, (uint32_t)k << 4);
+    };
+    auto seg_b = [&](SegIn &si) __attribute__((always_inline)) {
+        const int rr = si.rr;
+        si.dk = p.rrec[2 * (size_t)rr];
+        si.rx = p.rrec[2 * (size_t)rr + 1];
+        si.yr = GH ? Y.riv(rr) : *at(Y.y + 3 * (size_t)nown, (uint32_t)rr << 3);
+    };
+    // SEG_EARLY: only the edge-sharing instantiations (SH below) peel the first segment and issue it early.  In the
+    // others the early loads cost 2 VGPRs (and a wave per SIMD in three of them) or scratch, so their loop starts
+    // at the first segment; it still makes two round trips per segment instead of three.
+    constexpr bool SEG_EARLY = kShareOn(LCT, GH, LAKE, HYB, DIAG) && LSP != 0 && BS == kEleBS;
+    SegIn sg0 = {};
     const double infD = CL(infD), ThR = CL(ThetaR);
     const double infK = CL(infKsatV);
     const double fu_surf = fu.x, fu_sub = fu.y;
@@ -484,6 +523,7 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
                     dg.q_eta[i] = eta; dg.i_beta[i] = ibeta; }
     }
     stnt2(atw(p.cs[cur ^ 1], o16), satn, eic);
+    if (SEG_EARLY && nseg) seg_a(sfirst, sg0);
 
     // ---- Flux_Infiltration (Element.cpp:271-303) and Flux_Recharge (:304-335); zero on lake elements ----
     double qi = 0., qex = 0., qr = 0.;
@@ -529,34 +569,51 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
         lsp[0] = Es; lsp[kEleBS] = Eg; lsp[2 * kEleBS] = Tg; lsp[3 * kEleBS] = dsf_head; lsp[4 * kEleBS] = dgw_head;
         lspi[0] = cf;
     }
+    if (SEG_EARLY && nseg) seg_b(sg0);
     if (i < nown) __builtin_nontemporal_store(is_lake ? 0. : CDIV_SY(q_infil - q_rech - Eu - Tu), atw(dy + nown, o8));
 
     // ---- own river segments (fun_Seg_surface / fun_Seg_sub) and Qe2r (PassValue) ----
     const double dep = CLH(depression), rgh = CLH(rough);
     double qe2r_surf = 0., qe2r_sub = 0.;
+    // The first segment's loads are consumed here on every path (an empty asm that takes them as inputs).  They are
+    // issued and used under separate `if (nseg)` regions, and on the path the compiler cannot rule out — issued, the
+    // using region skipped — they would count as outstanding until their registers are next written: that put a
+    // full drain, the qseg2 store's acknowledgement included, in front of edge stage 1's loads.
+    if (SEG_EARLY)
+        asm volatile("" ::"v"(sg0.lc.x), "v"(sg0.lc.y), "v"(sg0.dk.x), "v"(sg0.dk.y), "v"(sg0.rx.x),
+                     "v"(__builtin_bit_cast(int2, sg0.rx.y).x), "v"(sg0.yr));
     if (nseg) {
         const double isf_seg = rmax(0., usf - q_infil + q_exfil);
-        for (int k = sfirst, k1 = k + nseg; k < k1; k++) {
-            // 20 B per segment streamed ({length, Cwr} + its reach); the reach's {depth, KsatH | BedThick, BC} is one
-            // 32-B record shared by the reach's ~5 segments (a gather beside the stage gather, mostly cache hits).
-            // (A 48-B segment record with the reach statics copied in, rounds 1-3: +153 MB of HBM per launch.)
-            const uint32_t k16 = (uint32_t)k << 4;
-            const double2 lc = *at(p.sg_lc, k16);
-            const int rr = *at(p.sg_r, (uint32_t)k << 2);
-            const double2 dk = p.rrec[2 * (size_t)rr], rx = p.rrec[2 * (size_t)rr + 1];
-            const int rbc = __builtin_bit_cast(int2, rx.y).x;
-            const double bt = rx.x;
-            // (the first segment's reach index + stage loaded at the top of the body instead, in flight across the
-            // vertical physics: 88 VGPRs, 0.625 vs 0.623 ms — not kept, profiles/r03/ab_river2/)
-            double yr = GH ? Y.riv(rr) : *at(Y.y + 3 * (size_t)nown, (uint32_t)rr << 3);   // uriv_of, BC below
+        // 20 B per segment streamed ({length, Cwr} + its reach); the reach's {depth, KsatH | BedThick, BC} is one
+        // 32-B record shared by the reach's ~5 segments (mostly cache hits).
+        // (A 48-B segment record with the reach statics copied in, rounds 1-3: +153 MB of HBM per launch.)
+        // A segment is two dependent round trips: {reach index, {length, Cwr}}, then {the reach record, its stage}.
+        // The stage is loaded from y unconditionally beside the record; a reach with a stage BC (rbc > 0) takes
+        // m.rybc afterwards.  The empty asm on the loaded stage keeps the two apart: without it the compiler folds them
+        // into one load from a selected address, which has to wait for the record (a third round trip).
+        auto seg_flux = [&](int k, const SegIn &si) __attribute__((always_inline)) {
+            const int rbc = __builtin_bit_cast(int2, si.rx.y).x;
+            const double bt = si.rx.x;
+            double yr = si.yr;                                          // uriv_of, BC below
+            asm volatile("" : "+v"(yr));
             if (MODE == 1) yr = (yr >= 0.) ? yr : 0.;
             if (rbc > 0) yr = m.rybc[rbc];
-            const double rdep = dk.x, L = lc.x;
-            const double qs = weir_jtoi(zs, isf_seg, zs - rdep, yr, zs + 0.0, lc.y, L, dep);
-            const double qg = r2e_gw(yr, zs - rdep, ugw, zb, ekh, dk.y, L, bt) * fu_sub;
-            *atw(p.qseg2, k16) = make_double2(qs, qg);                  // element-sorted
+            const double rdep = si.dk.x, L = si.lc.x;
+            const double qs = weir_jtoi(zs, isf_seg, zs - rdep, yr, zs + 0.0, si.lc.y, L, dep);
+            const double qg = r2e_gw(yr, zs - rdep, ugw, zb, ekh, si.dk.y, L, bt) * fu_sub;
+            *atw(p.qseg2, (uint32_t)k << 4) = make_double2(qs, qg);     // element-sorted
             qe2r_surf += -qs;
             qe2r_sub += -qg;
+        };
+        // SEG_EARLY: the element's first segment, whose two round trips were issued under the vertical physics
+        if (SEG_EARLY) seg_flux(sfirst, sg0);
+        // the other segments (all of them without SEG_EARLY): {index, length} together, then {record, stage} together
+#pragma unroll 1
+        for (int k = sfirst + (SEG_EARLY ? 1 : 0), k1 = sfirst + nseg; k < k1; k++) {
+            SegIn si;
+            seg_a(k, si);
+            seg_b(si);
+            seg_flux(k, si);
         }
     }
     if (DIAG) {
@@ -573,9 +630,10 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
     // edge is -qsf (else qsf), bit 1 its QeleSub before fu_Sub is -q (else q), bit 2 neither head difference is NaN.
     bool nan_q = false;
     const double isf = usf < 0. ? 0. : usf;
-    const double area = ldnt(at(p.area, o8));          // in flight across the edge loop
     const int n_edges = is_lake ? 0 : 3;               // lake elements: fun_Ele_lakeHorizon, all zero
     constexpr bool SH = kShareOn(LCT, GH, LAKE, HYB, DIAG) && LSP != 0 && BS == kEleBS;   // edge sharing, below
+    double area = 0.;                                  // in flight across the edge loop (SH: issued behind stage 1's loads)
+    if (!SH) area = ldnt(at(p.area, o8));
     // DEC: an instantiation without sharing that can run on a handle whose elements are stored in evaluation order
     // (the diagnostic replay, the ghost launches of a partition): it walks the reference slots and finds each one's
     // stored slot; on every other handle the order bits are zero and the stored slot is the reference slot
@@ -583,18 +641,29 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
     constexpr bool DEC = !SH && LCT && !LAKE && HYB == 0 && BS == kEleBS && (LSP == 1 || DIAG);
     [[maybe_unused]] const uint32_t evo = (uint32_t)sfl >> kEvoShift;   // order bits 0-2, bit 4: slot 2 is received
     // edge(s, j): the edge in stored slot s, which is reference slot j (SH: s is a literal and j is derived where needed)
-    auto edge = [&](int s, int j, double &qsf, double &q, uint32_t &sh) __attribute__((always_inline)) {
-        const int nb = s == 0 ? mt.x : s == 1 ? mt.y : mt.z;
-        const int nc = nb >= 0 ? nb : i;                  // boundary edge: harmless in-bounds loads
+    // edge_load(s): the five loads of stored slot s; edge_eval: the arithmetic on them
+    auto edge_load = [&](int s) __attribute__((always_inline)) {
+        EdgeIn e;
+        e.nb = s == 0 ? mt.x : s == 1 ? mt.y : mt.z;
+        const int nc = e.nb >= 0 ? e.nb : i;              // boundary edge: harmless in-bounds loads
         // (edge 0's loads issued right after the own record instead — held through the vertical physics — took
         // the kernel to 96 VGPRs with spills and measured 0.707 vs 0.617 ms, profiles/r03/ab_prologue/)
         const uint32_t n16 = (uint32_t)nc << 4, n8 = (uint32_t)nc << 3;
         // (a 32-bit byte offset: s is per lane under DEC, and a 64-bit pointer per lane cost a spilled VGPR and +3 %)
-        const double2 g = ldnt2(at(p.ged, o16 + (uint32_t)s * ((uint32_t)NEl << 4)));
-        const double2 nzz = *at(p.zz, n16);
-        const int ncf = *at((const int *)p.meta + 3, n16);
-        const double nsf_raw = GH ? Y.sf(nc) : *at(Y.y, n8);
-        const double ngw_raw = GH ? Y.gw(nc) : *at(Y.y + 2 * (size_t)nown, n8);
+        e.g = ldnt2(at(p.ged, o16 + (uint32_t)s * ((uint32_t)NEl << 4)));
+        e.nzz = *at(p.zz, n16);
+        e.ncf = *at((const int *)p.meta + 3, n16);
+        e.nsf_raw = GH ? Y.sf(nc) : *at(Y.y, n8);
+        e.ngw_raw = GH ? Y.gw(nc) : *at(Y.y + 2 * (size_t)nown, n8);
+        return e;
+    };
+    auto edge_eval = [&](int s, int j, const EdgeIn &e, double &qsf, double &q, uint32_t &sh)
+                         __attribute__((always_inline)) {
+        const int nb = e.nb;
+        [[maybe_unused]] const int nc = nb >= 0 ? nb : i;
+        const double2 g = e.g, nzz = e.nzz;
+        const int ncf = e.ncf;
+        const double nsf_raw = e.nsf_raw, ngw_raw = e.ngw_raw;
         const double B = g.x, d2n = g.y;
         const Recip R2 = recip_nr(d2n);                   // both Dist2Nabor divisions of the edge share 1/d2n
         qsf = 0.; q = 0.; sh = 0u;
@@ -671,6 +740,11 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
 #undef CN
 #undef CNH
     };
+    // edge(s, j): loads and arithmetic back to back
+    auto edge = [&](int s, int j, double &qsf, double &q, uint32_t &sh) __attribute__((always_inline)) {
+        const EdgeIn e = edge_load(s);
+        edge_eval(s, j, e, qsf, q, sh);
+    };
     double sumsurf = qe2r_surf, sumsub = qe2r_sub;     // QeleSurfTot = Qe2r + sum_j QeleSurf[j]
     auto add = [&](int j, double qsf, double q) __attribute__((always_inline)) {
         const double qsb = q * fu_sub;
@@ -712,20 +786,25 @@ __device__ __forceinline__ void ele_body(const DevMesh &m, const DevPacked &p, c
         lds_vd *xq = (lds_vd *)(lct + p.pt_off);
         lds_vb *xf = (lds_vb *)(lct + p.pt_off + 2 * kEleBS);
         const int tid = (int)threadIdx.x;
+        // each stage's loads are issued before the barrier in front of it (they touch no LDS, so the barrier does not
+        // order them): the wait for the workgroup's slowest wave and the loads' round trip overlap
+        const EdgeIn e0 = edge_load(0);
+        area = ldnt(at(p.area, o8));
         __syncthreads();                                  // every wave is past satKfun's pow-table reads
         {
             double qsf, q;
             uint32_t sh;
-            edge(0, 0, qsf, q, sh);
+            edge_eval(0, 0, e0, qsf, q, sh);
             xq[tid] = qsf;
             xq[kEleBS + tid] = q;
             xf[tid] = (unsigned char)sh;
         }
+        const EdgeIn e1 = edge_load(1);
         __syncthreads();                                  // the published edges are in LDS
         double a1, b1, a2 = 0., b2 = 0.;
         {
             uint32_t sh;
-            edge(1, 1, a1, b1, sh);
+            edge_eval(1, 1, e1, a1, b1, sh);
         }
         bool own2 = true;                                 // stored slot 2 is evaluated by this lane
         if (evo & (kEvoRcv2 >> kEvoShift)) {
