@@ -9,7 +9,12 @@
  *   WaterBalanceDiag::maybeWrite   :531-636 -> shud_wb_maybe_write  (residual pass at interval ends; only then the
  *                                              four residual arrays and the nine basin values come to the host)
  *   openFiles / writeDatHeader / writeDatRecord :90-150,258-369 -> shud_wb_create / shud_wb_maybe_write
- * Not restated: SHUD_WB_DIAG_QUAD (the CV_ONE_STEP monitor and basinwbfull_quad.dat).
+ *   SHUD_WB_DIAG_QUAD: openFiles :271,315,326-338,359-364 -> shud_wb_quad_enable (the sixth file,
+ *                                              <prefix>.basinwbfull_quad.dat); the basin rates of f()
+ *                                              (MD_f.cpp:57-86,115-128,193-213) and onCvodeMonitorStep :681-717
+ *                                              -> shud_wb_quad_step (a rates-only pass + the same reduction; the
+ *                                              trapezoid at the solver's own dt on device scalars); the quad row
+ *                                              of maybeWrite :597-623 -> shud_wb_maybe_write
  * Unsupported handles (SHUD_ERR_UNSUPPORTED): OMP semantics (the per-element ET terms exist only in the serial
  * path), lake models (the reference's diagnostic ignores lake storage), partitioned handles.
  *
@@ -17,6 +22,10 @@
  *   shud_rhs_summary, [shud_rhs_eval: the reference's extra, stateful f()], shud_rhs_refresh_diagnostics,
  *   shud_ode_get_dky(k = 1), shud_wb_sample, shud_wb_maybe_write, shud_out_export;
  * and shud_wb_on_et_update after every shud_et_step / shud_rhs_set_step_inputs that sets e_ic.
+ * With the quad monitor (shud.cpp:113-135) the integrator runs to tout one internal step at a time:
+ *   shud_ode_set_stop_time(tout); while (t + ZERO < tout) { shud_ode_solve(.., SHUD_ODE_ONE_STEP),
+ *   shud_rhs_eval (stateful, on the returned state), shud_rhs_refresh_diagnostics, shud_wb_quad_step(t) }
+ * and the per-solver-step calls above follow unchanged.
  */
 #ifndef SHUD_WB_H
 #define SHUD_WB_H
@@ -77,7 +86,9 @@ int shud_wb_on_et_update(shud_wb_t wb);
  * synchronisation.  A non-positive dt only records t. */
 int shud_wb_sample(shud_wb_t wb, double t, const double *d_dy);
 /* maybeWrite(t): 1 = a row was written (residuals formed, snapshots rolled, accumulators zeroed), 0 = not an
- * interval end, < 0 = error (SHUD_ERR_*).  Reads the handle's SHUD_ARR_Y_* arrays (shud_rhs_summary first). */
+ * interval end, < 0 = error (SHUD_ERR_*).  Reads the handle's SHUD_ARR_Y_* arrays (shud_rhs_summary first).
+ * With the quad monitor enabled the quad row (the basin row's dS and time) follows the basin row and the quad
+ * accumulators are zeroed; the previous quad rates and quad_last_t are kept. */
 int shud_wb_maybe_write(shud_wb_t wb, double t);
 /* host copies of the diagnostic's state (tests; synchronises the stream) */
 int shud_wb_read(shud_wb_t wb, ShudWbOut *out);
@@ -88,6 +99,24 @@ int shud_wb_destroy(shud_wb_t wb);
  * sample.  It integrates like shud_wb_sample (accumulators, sample time and previous rates move): use it on a
  * diagnostic made for timing only. */
 int shud_wb_time_samples(shud_wb_t wb, const double *d_dy, int reps, double *ms_sample);
+
+/* ---- SHUD_WB_DIAG_QUAD: the CV_ONE_STEP monitor ----
+ * Call once, after shud_wb_create and before the first shud_wb_sample / shud_wb_quad_step (otherwise SHUD_ERR_ARG):
+ * allocates the quad scalars (seven rates, previous rates and accumulators, all 0; quad_last_t = start_time), opens
+ * <prefix>.basinwbfull_quad.dat and writes its header (no file with a NULL prefix; SHUD_WB_ERR_IO if it cannot). */
+int shud_wb_quad_enable(shud_wb_t wb);
+/* onCvodeMonitorStep(t) on the flux arrays of the monitor's f() (shud_rhs_eval + shud_rhs_refresh_diagnostics
+ * first; SHUD_ERR_ARG on a handle that has no evaluation to replay or never refreshed): the seven basin rates, Qout
+ * as the sum of QrivDown over the outlet list, then acc += rate*dt on the first integrating step and
+ * acc += 0.5*(prev + rate)*dt on every later one, whatever ShudWbOptions.trapz says.  A non-positive dt only records
+ * t.  Stream-ordered, no host synchronisation; leaves the sample's accumulators and previous rates alone. */
+int shud_wb_quad_step(shud_wb_t wb, double t);
+/* host copies of the quad state (tests; synchronises the stream); any pointer may be NULL.  row: the last written
+ * quad row {dS, P, ET, Qout, Qedge, Qbc, Qss, noncons, resid}; last_t: quad_last_t */
+int shud_wb_read_quad(shud_wb_t wb, double acc[7], double rate[7], double row[9], double *last_t);
+/* measurement helper like shud_wb_time_samples: `reps` monitor passes (element pass, reach pass, finalize) with
+ * dt = 1 min; the quad accumulators, previous rates and quad_last_t move */
+int shud_wb_time_quad(shud_wb_t wb, int reps, double *ms_pass);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,15 @@
 // Bytes per element of the sample pass, counted from its loads and stores: DY 24, Sy + area 16, qElePrep +
 // qEleNetPrep 16, ic_raw 8, qEs..qTg 40, QeleSurfTot + QeleSubTot 16, flags 4, QeleSurf + QeleSub 48, four
 // accumulators read and written 64 = 236 B (trapezoid mode: + 64 for the four previous rates).
+//
+// The quad monitor (SHUD_WB_DIAG_QUAD; onCvodeMonitorStep :681-717 on the basin rates f() forms, MD_f.cpp:57-86,
+// 115-128,193-213) is a rates-only pass after every internal step of the integrator: k_wb_quad loads area, the
+// flag word, qElePrep, ic_raw, qEs..qTg and the six edge planes (8 + 4 + 8 + 8 + 40 + 48 = 116 B per element,
+// nothing stored per element), k_wb_quad_river copies QrivDown at the outlets and the reach boundary inflow (no
+// geometry, no Manning), both through block_partial into the sample's partial buffers (stream-ordered), and
+// finalize mode 3 forms the seven rates in the sample's order and applies Euler on the first integrating step, the
+// trapezoid on every later one, to device scalars of its own (d_qs).  Finalize mode 1 forms the quad row beside
+// the basin row and zeroes the quad accumulators.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,6 +50,9 @@ enum { RQ_QOUT = 0, RQ_RBC, RQ_STOR, RQ_N };
 // device scalars
 enum { S_RATE = 0, S_PREV = S_RATE + SHUD_WB_NBASIN, S_ACC = S_PREV + SHUD_WB_NBASIN, S_ROW = S_ACC + SHUD_WB_NBASIN,
        S_STOR_PREV = S_ROW + 9, S_STOR = S_STOR_PREV + 2, S_COUNT = S_STOR + 2 };
+// device scalars of the quad monitor (an array of their own, allocated by shud_wb_quad_enable)
+enum { Q_RATE = 0, Q_PREV = Q_RATE + SHUD_WB_NBASIN, Q_ACC = Q_PREV + SHUD_WB_NBASIN, Q_ROW = Q_ACC + SHUD_WB_NBASIN,
+       Q_COUNT = Q_ROW + 9 };
 // element flags word: bits 0-15 iBC (int16), bits 16-18 edge j has no neighbour (domain boundary), bit 19 iSS != 0
 constexpr int kFlagEdge = 16, kFlagSS = 19;
 // reach flags: bit 0 outlet (down < 0, not into a lake), bit 1 critical-depth outlet (down == -4)
@@ -178,6 +190,67 @@ __global__ void __launch_bounds__(kBS) k_wb_river(RivArgs a) {
     block_partial<RQ_N>(v, a.part, a.nblk);
 }
 
+struct QuadArgs {
+    int n;
+    const double *area;
+    const int *flags;
+    const double *prcp, *ic, *es, *eu, *eg, *tu, *tg, *qs, *qb, *eqbc;
+    double *part;
+    int nblk;
+};
+
+// the element half of the basin rates f() forms for the monitor (MD_f.cpp:57-86,115-128): k_wb_sample's basin terms
+// without its per-element rates and accumulators.  Lanes past n carry 0.0 to the barrier in block_partial.
+__global__ void __launch_bounds__(kBS) k_wb_quad(QuadArgs a) {
+    const int i = blockIdx.x * kBS + threadIdx.x;
+    double v[EQ_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < a.n) {
+        const size_t n = (size_t)a.n;
+        const double area = a.area[i];
+        const int fl = a.flags[i];
+        const double prcp = a.prcp[i], ic = a.ic[i];
+        const double es = ldn(a.es + i), eu = ldn(a.eu + i), eg = ldn(a.eg + i), tu = ldn(a.tu + i), tg = ldn(a.tg + i);
+        double qe[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) qe[j] = ldn(a.qs + j * n + i) + ldn(a.qb + j * n + i);
+        const int ibc = (int)(int16_t)(fl & 0xffff);
+        v[EQ_P] = prcp * area;
+        v[EQ_ET] = (ic + es + eu + eg + tu + tg) * area;
+        v[EQ_QBC] = ibc < 0 ? a.eqbc[-ibc] : 0.0;
+        v[EQ_QSS] = 0.0;                                               // QSS where iSS != 0: always 0.0
+        double nc = 0.0, qedge = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if ((fl >> (kFlagEdge + j)) & 1) qedge += qe[j];
+            else nc += qe[j];
+        }
+        v[EQ_NONCONS] = nc;
+        v[EQ_QEDGE] = qedge;
+    }
+    block_partial<EQ_N>(v, a.part, a.nblk);
+}
+
+struct QuadRivArgs {
+    int nr;
+    const int *flags, *bc;
+    const double *qdown, *rqbc;      // QrivDown of the monitor's f() (DevDiag), the reach flux table
+    double *part;
+    int nblk;
+};
+
+// the reach half (MD_f.cpp:193-205): QrivDown as f() computed it where the reach is an outlet, qBC where BC < 0;
+// partial slots RQ_QOUT and RQ_RBC
+__global__ void __launch_bounds__(kBS) k_wb_quad_river(QuadRivArgs a) {
+    const int r = blockIdx.x * kBS + threadIdx.x;
+    double v[2] = {0.0, 0.0};
+    if (r < a.nr) {
+        if (a.flags[r] & kRivOutlet) v[RQ_QOUT] = ldn(a.qdown + r);
+        const int bc = a.bc[r];
+        if (bc < 0) v[RQ_RBC] = a.rqbc[-bc];
+    }
+    block_partial<2>(v, a.part, a.nblk);
+}
+
 struct ResidArgs {
     int n;
     const double *sy, *area, *ysf, *yus, *ygw, *snow, *is;   // snow / is: nullptr reads as 0.0
@@ -220,11 +293,13 @@ __global__ void __launch_bounds__(256) k_wb_ic(int n, const double *__restrict__
 struct FinArgs {
     const double *epart, *rpart;
     int ne_q, nblk_e, nr_q, nblk_r;  // quantities and partials per quantity of the element / reach pass
-    int mode;                        // 0 sample, 1 write, 2 initial snapshot
+    int mode;                        // 0 sample, 1 write, 2 initial snapshot, 3 quad monitor step
     int open, trapz, has_prev;
     double dt;
     double *s;                       // device scalars [S_COUNT]
+    double *qs;                      // quad scalars [Q_COUNT]; nullptr: the monitor is off
 };
+static_assert(RQ_QOUT == 0 && RQ_RBC == 1, "k_wb_quad_river fills the first two reach partial slots");
 
 // the partials of every quantity in a fixed order (k_finalize's: kFinAcc interleaved accumulators per thread,
 // (a0 + a1) + (a2 + a3), wave64 butterfly, the wave results by one wave), then the scalar update by thread 0.
@@ -267,7 +342,7 @@ __global__ void __launch_bounds__(kFinThreads) k_wb_finalize(FinArgs f) {
     if (threadIdx.x != 0) return;
     double *s = f.s;
     const double *rt = tot + f.ne_q;
-    if (f.mode == 0) {               // sample :496-524
+    if (f.mode == 0 || f.mode == 3) {   // sample :496-524; the monitor's rates (MD_f.cpp:206-213) and step :702-715
         double rate[SHUD_WB_NBASIN];
         rate[SHUD_WB_P] = tot[EQ_P];
         rate[SHUD_WB_ET] = tot[EQ_ET];
@@ -276,6 +351,16 @@ __global__ void __launch_bounds__(kFinThreads) k_wb_finalize(FinArgs f) {
         rate[SHUD_WB_QBC] = tot[EQ_QBC] + rt[RQ_RBC];
         rate[SHUD_WB_QSS] = tot[EQ_QSS];
         rate[SHUD_WB_NONCONS] = tot[EQ_NONCONS];
+        if (f.mode == 3) {           // Euler on the first integrating step, then the trapezoid: no trapz switch here
+            double *q = f.qs;
+            for (int k = 0; k < SHUD_WB_NBASIN; k++) {
+                if (f.has_prev) q[Q_ACC + k] += 0.5 * (q[Q_PREV + k] + rate[k]) * f.dt;
+                else q[Q_ACC + k] += rate[k] * f.dt;
+                q[Q_PREV + k] = rate[k];
+                q[Q_RATE + k] = rate[k];
+            }
+            return;
+        }
         for (int k = 0; k < SHUD_WB_NBASIN; k++) {
             if (f.trapz && f.has_prev) s[S_ACC + k] += 0.5 * (s[S_PREV + k] + rate[k]) * f.dt;
             else s[S_ACC + k] += rate[k] * f.dt;
@@ -294,6 +379,16 @@ __global__ void __launch_bounds__(kFinThreads) k_wb_finalize(FinArgs f) {
             for (int k = 0; k < SHUD_WB_NBASIN; k++) s[S_ROW + 1 + k] = A[k];
             s[S_ROW + 8] = ds_total - net;
             for (int k = 0; k < SHUD_WB_NBASIN; k++) s[S_ACC + k] = 0.0;
+            if (f.qs) {              // the quad row :597-623: the same ds_total; the previous quad rates are kept
+                double *q = f.qs;
+                const double *B = q + Q_ACC;
+                const double qnet = B[SHUD_WB_P] + B[SHUD_WB_QBC] + B[SHUD_WB_QSS] - B[SHUD_WB_ET] - B[SHUD_WB_QOUT] -
+                                    B[SHUD_WB_QEDGE];
+                q[Q_ROW] = ds_total;
+                for (int k = 0; k < SHUD_WB_NBASIN; k++) q[Q_ROW + 1 + k] = B[k];
+                q[Q_ROW + 8] = ds_total - qnet;
+                for (int k = 0; k < SHUD_WB_NBASIN; k++) q[Q_ACC + k] = 0.0;
+            }
         }
         s[S_STOR_PREV] = s_ele;
         s[S_STOR_PREV + 1] = s_riv;
@@ -324,10 +419,17 @@ struct shud_wb {
     double *d_epart = nullptr, *d_rpart = nullptr, *d_s = nullptr;
     int nblk_e = 0, nblk_r = 0;
     double *h_row = nullptr;         // pinned: max(NE, S_COUNT) doubles (one residual array at a time, or the scalars)
-    FILE *fp[5] = {};
-    std::string fname[5];
+    FILE *fp[6] = {};                // [5]: basinwbfull_quad.dat (shud_wb_quad_enable)
+    std::string fname[6];
     int werr = 0;
     std::string werr_msg;
+    // quad monitor: quad_enabled, quad_last_t, quad_has_prev_rate; the scalars [Q_COUNT]; what its header repeats
+    bool quad = false, quad_has_prev = false, sampled = false;
+    double quad_last_t = 0.0;
+    double *d_qs = nullptr;
+    ShudWbOptions hdr{};
+    std::string hdr_mode, prefix;
+    bool have_prefix = false;
 
     template <class T>
     int dalloc(T **p, size_t n, const T *src = nullptr) {
@@ -414,7 +516,8 @@ static int wb_launch_storage(shud_wb *w, int mode) {
     HIP_TRY(hipGetLastError());
     int rc = wb_launch_river(w);
     if (rc) return rc;
-    FinArgs f{w->d_epart, w->d_rpart, 1, w->nblk_e, RQ_N, w->nblk_r, mode, w->open ? 1 : 0, 0, 0, 0.0, w->d_s};
+    FinArgs f{w->d_epart, w->d_rpart, 1, w->nblk_e, RQ_N, w->nblk_r, mode, w->open ? 1 : 0, 0, 0, 0.0, w->d_s,
+              w->quad ? w->d_qs : nullptr};
     hipLaunchKernelGGL(k_wb_finalize, dim3(1), dim3(kFinThreads), 0, h->stream, f);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -467,7 +570,13 @@ extern "C" int shud_wb_create(shud_rhs_t h, const ShudMeshSoA *m, const ShudPara
     w->open = m->close_boundary == 0;
     w->trapz = o->trapz != 0;
     w->interval = o->interval_min;
-    w->last_t = o->start_time;
+    w->last_t = w->quad_last_t = o->start_time;
+    w->hdr = *o;
+    w->hdr_mode = o->solar_lonlat_mode ? o->solar_lonlat_mode : "";
+    w->hdr.solar_lonlat_mode = w->hdr_mode.c_str();
+    w->have_prefix = o->prefix != nullptr;
+    w->prefix = o->prefix ? o->prefix : "";
+    w->hdr.prefix = nullptr;
     w->n_outlets = (int)outlets.size();
     w->nblk_e = blocks(NE); w->nblk_r = blocks(NR);
     const size_t E = (size_t)NE, R = (size_t)NR;
@@ -541,7 +650,7 @@ static int wb_sample_launch(shud_wb *w, double dt, const double *d_dy, bool has_
     int rc = wb_launch_river(w);
     if (rc) return rc;
     FinArgs f{w->d_epart, w->d_rpart, EQ_N, w->nblk_e, RQ_N, w->nblk_r, 0, w->open ? 1 : 0, w->trapz ? 1 : 0,
-              has_prev ? 1 : 0, dt, w->d_s};
+              has_prev ? 1 : 0, dt, w->d_s, nullptr};
     hipLaunchKernelGGL(k_wb_finalize, dim3(1), dim3(kFinThreads), 0, h->stream, f);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -550,6 +659,7 @@ static int wb_sample_launch(shud_wb *w, double dt, const double *d_dy, bool has_
 extern "C" int shud_wb_sample(shud_wb_t w, double t, const double *d_dy) {
     if (!w || !d_dy) return shud_fail(SHUD_ERR_ARG, "null argument");
     shud_rhs *h = w->h;
+    w->sampled = true;
     const double dt = t - w->last_t;
     if (!(dt > 0.0)) {               // :418-423
         w->last_t = t;
@@ -588,6 +698,11 @@ extern "C" int shud_wb_maybe_write(shud_wb_t w, double t) {
         HIP_TRY(hipMemcpyAsync(w->h_row, w->d_s + S_ROW, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         wb_record(w, 4, tq, 9, w->h_row);
+    }
+    if (w->fp[5]) {                  // :597-618, the basin row's t_quantized
+        HIP_TRY(hipMemcpyAsync(w->h_row, w->d_qs + Q_ROW, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        wb_record(w, 5, tq, 9, w->h_row);
     }
     if (w->werr) return shud_fail(w->werr, "shud_wb: %s", w->werr_msg.c_str());
     return 1;
@@ -644,7 +759,119 @@ extern "C" int shud_wb_time_samples(shud_wb_t w, const double *d_dy, int reps, d
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     w->last_t += 1.0 * (reps + 1);
+    w->sampled = true;
     *ms_sample = (double)ms / reps;
+    return rc;
+}
+
+// ---- SHUD_WB_DIAG_QUAD ----
+extern "C" int shud_wb_quad_enable(shud_wb_t w) {
+    if (!w) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (w->quad) return shud_fail(SHUD_ERR_ARG, "shud_wb_quad_enable: the monitor is already enabled");
+    if (w->sampled || w->rows > 0)
+        return shud_fail(SHUD_ERR_ARG, "shud_wb_quad_enable: call it before the first shud_wb_sample");
+    HIP_TRY(hipSetDevice(w->h->device));
+    int rc = w->dalloc(&w->d_qs, (size_t)Q_COUNT);
+    if (rc) return rc;
+    if (w->have_prefix) {
+        w->fname[5] = w->prefix + ".basinwbfull_quad.dat";
+        w->fp[5] = fopen(w->fname[5].c_str(), "wb");
+        if (!w->fp[5]) return shud_fail(SHUD_WB_ERR_IO, "shud_wb_quad_enable: cannot open %s", w->fname[5].c_str());
+        wb_header(w, 5, "basinwbfull_quad (m3)", 9, &w->hdr);
+    }
+    w->quad = true;
+    return SHUD_OK;
+}
+
+static int wb_quad_launch(shud_wb *w, double dt, bool has_prev) {
+    shud_rhs *h = w->h;
+    const DevDiag &g = h->dd;
+    QuadArgs a{w->NE, w->d_area, w->d_flags, h->dm.prcp, w->d_ic, g.q_es, g.q_eu, g.q_eg, g.q_tu, g.q_tg,
+               g.qele_surf, g.qele_sub, h->dm.eqbc, w->d_epart, w->nblk_e};
+    hipLaunchKernelGGL(k_wb_quad, dim3(w->nblk_e), dim3(kBS), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (w->NR > 0) {
+        QuadRivArgs r{w->NR, w->d_rflags, w->d_rbc, g.qriv_down, h->dm.rqbc, w->d_rpart, w->nblk_r};
+        hipLaunchKernelGGL(k_wb_quad_river, dim3(w->nblk_r), dim3(kBS), 0, h->stream, r);
+        HIP_TRY(hipGetLastError());
+    }
+    FinArgs f{w->d_epart, w->d_rpart, EQ_N, w->nblk_e, 2, w->nblk_r, 3, w->open ? 1 : 0, 1, has_prev ? 1 : 0, dt,
+              w->d_s, w->d_qs};
+    hipLaunchKernelGGL(k_wb_finalize, dim3(1), dim3(kFinThreads), 0, h->stream, f);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the handle holds flux arrays some f() left: an evaluation to replay exists and the refresh has run at least once
+// (its ET sums exist).  A refresh older than the last evaluation cannot be told from a current one.
+static bool wb_have_fluxes(const shud_rhs *h) { return h->have_diag && h->have_last && h->d_trans != nullptr; }
+
+extern "C" int shud_wb_quad_step(shud_wb_t w, double t) {
+    if (!w) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (!w->quad) return shud_fail(SHUD_ERR_ARG, "shud_wb_quad_step: call shud_wb_quad_enable first");
+    shud_rhs *h = w->h;
+    const double dt = t - w->quad_last_t;
+    if (!(dt > 0.0)) {               // :690-694: the previous rates and has_prev stay
+        w->quad_last_t = t;
+        return SHUD_OK;
+    }
+    if (!wb_have_fluxes(h))
+        return shud_fail(SHUD_ERR_ARG, "shud_wb_quad_step: call shud_rhs_eval and shud_rhs_refresh_diagnostics first");
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = wb_quad_launch(w, dt, w->quad_has_prev);
+    if (rc) return rc;
+    w->quad_has_prev = true;
+    w->quad_last_t = t;
+    return SHUD_OK;
+}
+
+extern "C" int shud_wb_read_quad(shud_wb_t w, double acc[7], double rate[7], double row[9], double *last_t) {
+    if (!w) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (!w->quad) return shud_fail(SHUD_ERR_ARG, "shud_wb_read_quad: the monitor is not enabled");
+    shud_rhs *h = w->h;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    double q[Q_COUNT];
+    HIP_TRY(hipMemcpy(q, w->d_qs, sizeof(q), hipMemcpyDeviceToHost));
+    for (int k = 0; k < SHUD_WB_NBASIN; k++) {
+        if (acc) acc[k] = q[Q_ACC + k];
+        if (rate) rate[k] = q[Q_RATE + k];
+    }
+    if (row)
+        for (int k = 0; k < 9; k++) row[k] = q[Q_ROW + k];
+    if (last_t) *last_t = w->quad_last_t;
+    return SHUD_OK;
+}
+
+// Measurement helper (tools/wb_sample_time.py): `reps` monitor passes with dt = 1 between HIP events; the quad
+// accumulators, previous rates and quad_last_t move.
+extern "C" int shud_wb_time_quad(shud_wb_t w, int reps, double *ms_pass) {
+    if (!w || !ms_pass || reps < 1) return shud_fail(SHUD_ERR_ARG, "bad argument");
+    if (!w->quad) return shud_fail(SHUD_ERR_ARG, "shud_wb_time_quad: call shud_wb_quad_enable first");
+    shud_rhs *h = w->h;
+    if (!wb_have_fluxes(h)) return shud_fail(SHUD_ERR_ARG, "shud_wb_time_quad: diagnostics arrays missing");
+    HIP_TRY(hipSetDevice(h->device));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.f;
+    auto timed = [&]() -> int {
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        int rc = wb_quad_launch(w, 1.0, w->quad_has_prev);          // warm-up
+        if (rc) return rc;
+        w->quad_has_prev = true;
+        HIP_TRY(hipEventRecord(e0, h->stream));
+        for (int k = 0; k < reps; k++)
+            if ((rc = wb_quad_launch(w, 1.0, true))) return rc;
+        HIP_TRY(hipEventRecord(e1, h->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        return 0;
+    };
+    const int rc = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    w->quad_last_t += 1.0 * (reps + 1);
+    *ms_pass = (double)ms / reps;
     return rc;
 }
 
@@ -652,7 +879,7 @@ extern "C" int shud_wb_destroy(shud_wb_t w) {
     if (!w) return SHUD_OK;
     (void)hipSetDevice(w->h->device);
     (void)hipStreamSynchronize(w->h->stream);
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < 6; k++) {
         if (!w->fp[k]) continue;
         if (fflush(w->fp[k]) != 0 || ferror(w->fp[k])) wb_werr(w, "flush error on " + w->fname[k]);
         if (fclose(w->fp[k]) != 0) wb_werr(w, "close error on " + w->fname[k]);

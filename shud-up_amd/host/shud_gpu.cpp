@@ -19,8 +19,13 @@
 // With SHUD_WB_DIAG set (env_truthy, WaterBalanceDiag.cpp:21-36, after shud.cpp:72's test) the water-balance
 // diagnostics of shud.cpp:70-75,110-112,137-152 run on the device (include/shud_wb.h): onETUpdate after every ET
 // step; after summary the extra, stateful f() on the accepted state, CVodeGetDky(k = 1), sample and maybeWrite,
-// then ExportResults.  SHUD_WB_DIAG_TRAPZ selects the trapezoid rule; SHUD_WB_DIAG_QUAD is not supported (one line
-// says so).  Without SHUD_WB_DIAG the loop makes exactly the calls it made before.
+// then ExportResults.  SHUD_WB_DIAG_TRAPZ selects the trapezoid rule.  SHUD_WB_DIAG_QUAD (read only when
+// SHUD_WB_DIAG is on) runs the monitor of shud.cpp:113-135: the stop time is always set and the integrator goes to
+// tout one internal step at a time (CV_ONE_STEP), each followed by a stateful f() on the returned state, its flux
+// arrays and shud_wb_quad_step; <prj>.basinwbfull_quad.dat is written beside basinwbfull.dat.  These f() calls move
+// the carried state, so the trajectory differs from a run without QUAD, as in the reference.  Without
+// SHUD_WB_DIAG the loop makes exactly the calls it made before, and without SHUD_WB_DIAG_QUAD exactly those of
+// SHUD_WB_DIAG alone.
 // Not restated (out of the device path's scope): flood alerts, the screen print / .cfg.ic.update snapshots,
 // NetCDF forcing and outputs, the uncoupled -g mode.
 #include <strings.h>
@@ -197,10 +202,11 @@ int main(int argc, char **argv) {
     // ---- WaterBalanceDiag::enable (shud.cpp:70-75): shud.cpp:72's test, then openFiles' env_truthy ----
     shud_wb_t wb = nullptr;
     double *d_du = nullptr;
+    bool quad = false;
+    long long quad_steps = 0;
     const char *wb_env = getenv("SHUD_WB_DIAG");
     if (wb_env != nullptr && wb_env[0] != '\0' && strcmp(wb_env, "0") != 0 && env_truthy(wb_env)) {
-        if (env_truthy(getenv("SHUD_WB_DIAG_QUAD")))
-            fprintf(stderr, "shud_gpu: SHUD_WB_DIAG_QUAD is not supported; running without the CV_ONE_STEP monitor\n");
+        quad = env_truthy(getenv("SHUD_WB_DIAG_QUAD"));       // read only when the diagnostic is on (:271)
         const std::string prefix = outdir + "/" + prj;
         ShudWbOptions wo = {c.start_time, shud_project_wb_interval(p), env_truthy(getenv("SHUD_WB_DIAG_TRAPZ")) ? 1 : 0,
                             (int64_t)c.forc_start_time, c.radiation_input_mode, c.terrain_radiation,
@@ -208,6 +214,10 @@ int main(int argc, char **argv) {
         if (shud_wb_create(h, &mesh, &par, &wo, &wb) ||
             shud_rhs_device_alloc(h, (size_t)ny * sizeof(double), (void **)&d_du)) {
             fprintf(stderr, "shud_wb_create: %s\n", shud_rhs_last_error_string());
+            return 1;
+        }
+        if (quad && shud_wb_quad_enable(wb)) {
+            fprintf(stderr, "shud_wb_quad_enable: %s\n", shud_rhs_last_error_string());
             return 1;
         }
     }
@@ -220,7 +230,8 @@ int main(int argc, char **argv) {
     const long long nsteps = max_steps >= 0 && max_steps < c.num_steps ? max_steps : c.num_steps;
     int rc = 0;
     // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
-    double ph[6] = {0, 0, 0, 0, 0, 0};      // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag
+    // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag, quad monitor (its f(), replay and pass)
+    double ph[7] = {0, 0, 0, 0, 0, 0, 0};
     auto tick = std::chrono::steady_clock::now();
     auto lap = [&](int k) {
         const auto now = std::chrono::steady_clock::now();
@@ -260,8 +271,30 @@ int main(int argc, char **argv) {
                 }
                 lap(5);
             }
-            if (et_sub) shud_ode_set_stop_time(ode, tout);
-            const int flag = shud_ode_solve(ode, tout, d_y, SHUD_WHERE_DEVICE, &t, SHUD_ODE_NORMAL);
+            if (et_sub || quad) shud_ode_set_stop_time(ode, tout);
+            int flag = 0;
+            if (quad) {
+                // shud.cpp:121-129: CV_ONE_STEP to tout; after every internal step f(t, udata, du, MD) on the
+                // returned state (stateful, like the sample's extra f()), its flux arrays, onCvodeMonitorStep(t)
+                while (t + kZero < tout) {
+                    flag = shud_ode_solve(ode, tout, d_y, SHUD_WHERE_DEVICE, &t, SHUD_ODE_ONE_STEP);
+                    if (flag < 0) break;
+                    lap(2);
+                    int qrc = shud_rhs_eval(h, t, d_y, d_du, SHUD_WHERE_DEVICE);
+                    if (!qrc) qrc = shud_rhs_refresh_diagnostics(h);
+                    if (!qrc) qrc = shud_wb_quad_step(wb, t);
+                    if (qrc) {
+                        fprintf(stderr, "quad monitor: %s (code %d)\n", shud_rhs_last_error_string(), qrc);
+                        rc = 1;
+                        break;
+                    }
+                    quad_steps++;
+                    lap(6);
+                }
+                if (rc) break;
+            } else {
+                flag = shud_ode_solve(ode, tout, d_y, SHUD_WHERE_DEVICE, &t, SHUD_ODE_NORMAL);
+            }
             if (flag < 0) {
                 ShudErr e;
                 shud_rhs_get_error(h, &e);
@@ -319,14 +352,21 @@ int main(int argc, char **argv) {
                "%d outputs  wall %.2f s (time loop %.2f s)\n",
                t, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni, (long long)st.nli,
                (long long)st.netf, nprint, wall, loop_s);
-    // one machine-readable line (tools/e2e.sh)
+    // one machine-readable line (tools/e2e.sh); the quad monitor's phase and step count appear only
+    // when it ran
+    char quad_txt[48] = "", quad_n[48] = "";
+    if (quad) {
+        snprintf(quad_txt, sizeof(quad_txt), ", \"wb_quad\": %.4f", ph[6]);
+        snprintf(quad_n, sizeof(quad_n), "\"quad_steps\": %lld, ", quad_steps);
+    }
     printf("{\"shud_gpu\": {\"num_ele\": %d, \"t_end_min\": %.6f, \"solver_steps\": %lld, \"cvode_steps\": %lld, "
            "\"rhs_evals\": %lld, \"newton_iters\": %lld, \"krylov_iters\": %lld, \"outputs\": %d, "
            "\"wall_s\": %.4f, \"loop_s\": %.4f, \"loop_phases_s\": {\"forcing\": %.4f, \"et_step\": %.4f, "
-           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f}, \"host_syncs\": %lld, "
-           "\"exit\": %d}}\n",
+           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f%s}, \"host_syncs\": %lld, "
+           "%s\"exit\": %d}}\n",
            mesh.num_ele, t, nsteps, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni,
-           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], (long long)st.n_sync, rc);
+           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], quad_txt,
+           (long long)st.n_sync, quad_n, rc);
     shud_ode_destroy(ode);
     shud_rhs_device_free(h, d_y);
     if (d_du) shud_rhs_device_free(h, d_du);

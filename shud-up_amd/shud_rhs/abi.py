@@ -279,6 +279,10 @@ WB_FUNCTIONS = {
     "shud_wb_read": (C.c_int, [_H, C.POINTER(ShudWbOut)]),
     "shud_wb_destroy": (C.c_int, [_H]),
     "shud_wb_time_samples": (C.c_int, [_H, C.c_void_p, C.c_int, c_double_p]),
+    "shud_wb_quad_enable": (C.c_int, [_H]),
+    "shud_wb_quad_step": (C.c_int, [_H, C.c_double]),
+    "shud_wb_read_quad": (C.c_int, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "shud_wb_time_quad": (C.c_int, [_H, C.c_int, c_double_p]),
 }
 
 

@@ -447,6 +447,29 @@ class WaterBalance:
         _check(lib().shud_wb_time_samples(self.h, C.c_void_p(d_dy), int(reps), C.byref(ms)), "shud_wb_time_samples")
         return ms.value
 
+    def quad_enable(self):
+        """SHUD_WB_DIAG_QUAD: the CV_ONE_STEP monitor and <prefix>.basinwbfull_quad.dat; once, before the first
+        sample"""
+        _check(lib().shud_wb_quad_enable(self.h), "shud_wb_quad_enable")
+
+    def quad_step(self, t):
+        """onCvodeMonitorStep(t) on the flux arrays of the monitor's f() (eval_device + refresh_diagnostics first)"""
+        _check(lib().shud_wb_quad_step(self.h, float(t)), "shud_wb_quad_step")
+
+    def read_quad(self):
+        """dict of host copies: the seven quad accumulators, the rates of the last integrating monitor step, the
+        last written quad row, quad_last_t"""
+        acc, rate, row, last_t = np.zeros(7), np.zeros(7), np.zeros(9), C.c_double()
+        _check(lib().shud_wb_read_quad(self.h, acc.ctypes.data_as(abi.c_double_p), rate.ctypes.data_as(abi.c_double_p),
+                                       row.ctypes.data_as(abi.c_double_p), C.byref(last_t)), "shud_wb_read_quad")
+        return {"acc": acc, "rate": rate, "row": row, "last_t": last_t.value}
+
+    def time_quad(self, reps):
+        """milliseconds per monitor pass over `reps` passes (HIP events; shud_wb_time_quad)"""
+        ms = C.c_double()
+        _check(lib().shud_wb_time_quad(self.h, int(reps), C.byref(ms)), "shud_wb_time_quad")
+        return ms.value
+
     def close(self):
         """shud_wb_destroy; raises on a write error.  Call before the handle's close()."""
         if self.h:

@@ -49,20 +49,28 @@ class ShudSolver:
         self.ode = OdeSolver(handle, ctl.start, y0, ctl.reltol, ctl.abstol, ctl.init_step, ctl.max_step,
                              ctl.min_step, ctl.max_num_steps)
         self.y = None
+        self.quad_steps = 0             # monitor steps of run(quad=True)
 
-    def run(self, num_steps, forcing=None, on_output=None, output=None, wb=None):
+    def run(self, num_steps, forcing=None, on_output=None, output=None, wb=None, quad=False):
         """num_steps solver steps (the reference's NumSteps loop); on_output(i, t, y) after each (host copy of y).
         output: runtime.Output whose controls point at the handle's device arrays — after each solver step
         summary(udata) + ExportResults(t) run on the device (shud.cpp:137,153): no host copy of y at all.
         wb: runtime.WaterBalance (needs output) — the reference's SHUD_WB_DIAG hooks (shud.cpp:110-112,137-152):
         onETUpdate after every ET step; after summary the extra, stateful f() on the accepted state, CVodeGetDky(k = 1),
         sample and maybeWrite, then ExportResults.  The extra f() advances the carried state: the trajectory differs
-        from a run without wb, as in the reference."""
+        from a run without wb, as in the reference.
+        quad: SHUD_WB_DIAG_QUAD (needs wb, with wb.quad_enable() called) — the reference's CV_ONE_STEP loop
+        (shud.cpp:113-135): the stop time is always set, the integrator returns after every internal step, and each
+        is followed by a stateful f() on the returned state, its flux arrays and wb.quad_step(t); self.quad_steps
+        counts them.  These f() calls advance the carried state too: the trajectory differs from a run with wb
+        alone, as in the reference."""
         ctl = self.ctl
         tnext = self.t
         d_y = None
         if wb is not None and output is None:
             raise ValueError("wb needs output (the device-resident loop)")
+        if quad and wb is None:
+            raise ValueError("quad needs wb")
         if output is not None:
             d_y = self._out_y = getattr(self, "_out_y", None) or self.h.device_alloc(8 * self.h.num_y)
         d_du = None
@@ -78,19 +86,26 @@ class ShudSolver:
                         self.h.et_step(f)
                 if wb is not None:
                     wb.on_et_update()
-                if ctl.et_substep:
+                if ctl.et_substep or quad:
                     self.ode.set_stop_time(tout)
+                if quad:
+                    # shud.cpp:121-129: one internal step at a time; f() on the returned state (stateful, like the
+                    # sample's extra f()), its flux arrays, onCvodeMonitorStep(t)
+                    while self.t + ZERO < tout:
+                        flag, t = self.ode.solve_device(tout, d_y, one_step=True)
+                        self._check_flag(flag, t)
+                        self.t, self.y = t, None
+                        self.h.eval_device(t, d_y, d_du)
+                        self.h.refresh_diagnostics()
+                        wb.quad_step(t)
+                        self.quad_steps += 1
+                    continue
                 if d_y is not None:
                     flag, t = self.ode.solve_device(tout, d_y)
                     y = None
                 else:
                     flag, t, y = self.ode.solve(tout)
-                if flag < 0:
-                    if flag == abi.ODE_RHSFUNC_FAIL:
-                        e = self.h.get_error()
-                        if e["exit_code"]:
-                            raise ShudRhsError(abi.SHUD_ERR_PHYSICS, e["message"], e)
-                    raise RuntimeError(f"CVode failed with flag {flag} at t={t}")
+                self._check_flag(flag, t)
                 self.t, self.y = t, y
             if output is not None:
                 # Model_Data::summary(udata) on y(tout); the flux arrays are those of CVODE's last f() call,
@@ -110,6 +125,14 @@ class ShudSolver:
                     self.y = self.h.d2h(np.empty(self.h.num_y), d_y)
                 on_output(i, self.t, self.y)
         return self.t, self.y
+
+    def _check_flag(self, flag, t):
+        if flag < 0:
+            if flag == abi.ODE_RHSFUNC_FAIL:
+                e = self.h.get_error()
+                if e["exit_code"]:
+                    raise ShudRhsError(abi.SHUD_ERR_PHYSICS, e["message"], e)
+            raise RuntimeError(f"CVode failed with flag {flag} at t={t}")
 
     def stats(self):
         return self.ode.stats()

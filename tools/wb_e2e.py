@@ -1,6 +1,7 @@
 """shud_gpu on a synthetic 2000-element project (one day) with the water-balance diagnostics off and on: the
 per-phase wall times of its loop, and the basin residual of the diagnostic run relative to the accumulated
-precipitation (basinwbfull.dat column 9 against column 2, summed over the rows).
+precipitation (basinwbfull.dat column 9 against column 2, summed over the rows).  A fourth run adds the quad monitor
+(SHUD_WB_DIAG_QUAD=1): its phase time and the residuals of basinwbfull.dat and basinwbfull_quad.dat of that one run.
 
 usage: python tools/wb_e2e.py [--n-ele 2000] [--days 1.0] [--workdir DIR]      -> one JSON line"""
 import argparse
@@ -37,7 +38,8 @@ def main():
     base = {k: v for k, v in os.environ.items() if not k.startswith("SHUD_WB_DIAG")}
     res = {}
     for name, env in (("off", base), ("on", dict(base, SHUD_WB_DIAG="1")),
-                      ("on_trapz", dict(base, SHUD_WB_DIAG="1", SHUD_WB_DIAG_TRAPZ="1"))):
+                      ("on_trapz", dict(base, SHUD_WB_DIAG="1", SHUD_WB_DIAG_TRAPZ="1")),
+                      ("on_quad", dict(base, SHUD_WB_DIAG="1", SHUD_WB_DIAG_QUAD="1"))):
         out = os.path.join(work, "out_" + name)
         j = run(src, out, env)
         res[name] = {"loop_s": j["loop_s"], "phases_s": j["loop_phases_s"],
@@ -49,6 +51,17 @@ def main():
                                   "resid_over_P": float(b[:, 8].sum() / b[:, 1].sum()),
                                   "max_row_resid_over_P": float(abs(b[:, 8]).max() / b[:, 1].sum()),
                                   "rows_m3": [[float(x) for x in row] for row in b[:3]]}
+            if name == "on_quad":
+                # the same run's two basin files: Euler at the solver steps against the trapezoid at the
+                # integrator's own steps; first row and whole run
+                q = shudio.read_dat(os.path.join(out, "syn.basinwbfull_quad.dat"))["data"]
+                res[name]["quad_steps"] = j["quad_steps"]
+                res[name]["cvode_steps"] = j["cvode_steps"]
+                res[name]["quad"] = {"rows": int(q.shape[0]), "first_row_m3": [float(x) for x in q[0]],
+                                     "first_row_resid_m3": float(q[0, 8]), "basin_first_row_resid_m3": float(b[0, 8]),
+                                     "first_row_ratio": float(abs(q[0, 8]) / abs(b[0, 8])) if b[0, 8] else None,
+                                     "resid_m3": float(q[:, 8].sum()), "basin_resid_m3": float(b[:, 8].sum()),
+                                     "resid_over_P": float(q[:, 8].sum() / q[:, 1].sum())}
             for key in ("elewb3_resid", "elewb3_budget_resid", "elewbfull_resid", "elewbfull_budget_resid"):
                 e = shudio.read_dat(os.path.join(out, f"syn.{key}.dat"))["data"]
                 res[name][key + "_max_abs_m"] = float(abs(e).max())

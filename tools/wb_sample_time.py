@@ -4,6 +4,8 @@ bytes the element pass moves (counted from its loads and stores, csrc/shud_wb.hi
 the trapezoid rule's previous-rate arrays).  Also holds three basin sums of the timed mesh to the bound every
 summation order meets, |gpu - fsum(terms)| <= (n - 1) 2^-53 sum|terms| (at 10M elements the finalize kernel's
 loop makes three trips; tests/test_gpu_wb.py holds all nine sums to the bound up to 4.25M elements).
+The quad monitor's pass (shud_wb_time_quad, 116 B per element) is timed in the same process between two timings of
+the sample pass, and two of its rates are held to the same bound.
 
 usage: python tools/wb_sample_time.py [--n-ele 10000000] [--reps 20]      -> one JSON line (Euler and trapezoid)"""
 import argparse
@@ -21,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "shud-up_amd"))
 from shud_rhs import abi, runtime, synth, workload  # noqa: E402
 
 BYTES_EULER, BYTES_TRAPZ = 236, 300
+BYTES_QUAD = 116          # k_wb_quad: area 8, flags 4, qElePrep 8, ic_raw 8, qEs..qTg 40, QeleSurf + QeleSub 48
 
 
 def main():
@@ -71,7 +74,27 @@ def main():
     wb.on_et_update()
     ms_t = wb.time_samples(d_f, a.reps)
     wb.close()
-    out = {"wb_sample": {"num_ele": NE, "num_riv": m.num_riv, "reps": a.reps,
+    # the quad monitor's pass (shud_wb_quad_step: rates only, nothing stored per element) and, in the same process
+    # and on the same arrays, the sample pass again right before and after it
+    wb = runtime.WaterBalance(h, 60)
+    wb.quad_enable()
+    wb.on_et_update()
+    ms_s1 = wb.time_samples(d_f, a.reps)
+    ms_q = wb.time_quad(a.reps)
+    ms_s2 = wb.time_samples(d_f, a.reps)
+    ms_q2 = wb.time_quad(a.reps)
+    qrate = wb.read_quad()["rate"]
+    wb.close()
+    for k, idx in (("P", abi.SHUD_WB_P), ("ET", abi.SHUD_WB_ET)):
+        ref, s_abs = math.fsum(terms[k]), math.fsum(np.abs(terms[k]))
+        bound = (terms[k].size - 1) * 2.0 ** -53 * s_abs
+        checks["quad_" + k] = {"gpu": qrate[idx], "fsum": ref, "abs_diff": abs(qrate[idx] - ref), "bound": bound,
+                               "ok": bool(abs(qrate[idx] - ref) <= bound and s_abs > 0)}
+    quad = {"ms_per_pass": [ms_q, ms_q2], "bytes_per_element": BYTES_QUAD,
+            "TBps": BYTES_QUAD * NE / (min(ms_q, ms_q2) * 1e-3) / 1e12,
+            "sample_ms_same_process": [ms_s1, ms_s2],
+            "sample_TBps_same_process": BYTES_EULER * NE / (min(ms_s1, ms_s2) * 1e-3) / 1e12}
+    out = {"wb_sample": {"num_ele": NE, "num_riv": m.num_riv, "reps": a.reps, "quad": quad,
                          "euler": {"ms_per_sample": ms, "bytes_per_element": BYTES_EULER,
                                    "TBps": BYTES_EULER * NE / (ms * 1e-3) / 1e12},
                          "trapz": {"ms_per_sample": ms_t, "bytes_per_element": BYTES_TRAPZ,
