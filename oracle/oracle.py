@@ -154,21 +154,22 @@ class OracleEt:
 class OracleOde:
     """CPU restatement of the CVODE 6.0.0 BDF/Newton/SPGMR integrator (shud_oracle_ode.c).
 
-    rhs: an OracleRhs (the SHUD RHS) or a built-in test problem "robertson" / "decay" / "decayn"."""
+    rhs: an OracleRhs (the SHUD RHS) or a built-in test problem "robertson" / "decay" / "decayn".
+    maxl: SPGMR Krylov dimension (0: 5); max_order: CVodeSetMaxOrd (0: 5)."""
 
     STATS = ["nst", "nfe", "nfe_ls", "nni", "ncfn", "nnf", "netf", "nsetups", "nli", "ncfl", "njtimes", "qlast",
              "qcur"]
     RSTATS = ["hlast", "hcur", "tcur", "hnext"]
 
     def __init__(self, rhs, t0, y0, rtol, atol, init_step, max_step=0.0, min_step=1e-6, max_num_steps=1000000,
-                 maxl=0):
+                 maxl=0, max_order=0):
         L = lib()
         if not getattr(L, "_ode_bound", False):
             vp, d, lg = C.c_void_p, C.c_double, C.c_long
             L.oracle_ode_create_shud.restype = vp
-            L.oracle_ode_create_shud.argtypes = [vp, lg, d, vp, d, d, d, d, d, lg, C.c_int]
+            L.oracle_ode_create_shud.argtypes = [vp, lg, d, vp, d, d, d, d, d, lg, C.c_int, C.c_int]
             L.oracle_ode_create_test.restype = vp
-            L.oracle_ode_create_test.argtypes = [C.c_int, lg, d, vp, d, d, d, d, d, lg, C.c_int]
+            L.oracle_ode_create_test.argtypes = [C.c_int, lg, d, vp, d, d, d, d, d, lg, C.c_int, C.c_int]
             L.oracle_ode_solve.restype = C.c_int
             L.oracle_ode_solve.argtypes = [vp, d, vp, C.POINTER(d), C.c_int]
             L.oracle_ode_get_dky.restype = C.c_int
@@ -181,7 +182,7 @@ class OracleOde:
         self._y0 = np.ascontiguousarray(y0, dtype=np.float64).copy()
         self.n = self._y0.size
         args = (float(t0), self._y0.ctypes.data, float(rtol), float(atol), float(init_step), float(max_step),
-                float(min_step), int(max_num_steps), int(maxl))
+                float(min_step), int(max_num_steps), int(maxl), int(max_order))
         if isinstance(rhs, str):
             prob = {"robertson": 1, "decay": 2, "decayn": 3}[rhs]
             self.h = L.oracle_ode_create_test(prob, self.n, *args)

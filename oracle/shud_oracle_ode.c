@@ -216,6 +216,9 @@ static double device_order_sum(long n, const double *term) {
     return waves_in_order(lanes, ORACLE_FIN_THREADS);
 }
 
+/* the device order by itself (tests/test_ode_kernels.py pins the numpy restatement against it) */
+double oracle_ode_device_order_sum(long n, const double *term) { return device_order_sum(n, term); }
+
 static double *g_term = NULL;
 static long g_term_n = 0;
 static double *term_buf(long n) {
@@ -1025,9 +1028,10 @@ static int shud_rhs_adapter(double t, const double *y, double *ydot, void *user)
 }
 
 OracleOde *oracle_ode_create_shud(OracleModel *M, long ny, double t0, const double *y0, double rtol, double atol,
-                                  double init_step, double max_step, double min_step, long max_num_steps, int maxl) {
+                                  double init_step, double max_step, double min_step, long max_num_steps, int maxl,
+                                  int max_order) {
     return oracle_ode_create(ny, shud_rhs_adapter, M, t0, y0, rtol, atol, init_step, max_step, min_step,
-                             max_num_steps, maxl, QMAX);
+                             max_num_steps, maxl, max_order);
 }
 
 /* published test problems (known answers: tests/test_ode.py) */
@@ -1062,19 +1066,21 @@ static int decayn_rhs(double t, const double *y, double *yd, void *user) {      
 }
 static long decayn_n = 0;
 
-/* problem 1 = Robertson (n = 3), 2 = three-rate decay (n = 3), 3 = n-component seven-rate decay */
+/* problem 1 = Robertson (n = 3), 2 = three-rate decay (n = 3), 3 = n-component seven-rate decay;
+ * max_order: CVodeSetMaxOrd (<= 0 or > 5: 5) */
 OracleOde *oracle_ode_create_test(int problem, long n, double t0, const double *y0, double rtol, double atol,
-                                  double init_step, double max_step, double min_step, long max_num_steps, int maxl) {
+                                  double init_step, double max_step, double min_step, long max_num_steps, int maxl,
+                                  int max_order) {
     if (problem == 3) {
         decayn_n = n;
         return oracle_ode_create(n, decayn_rhs, (void *)&decayn_n, t0, y0, rtol, atol, init_step, max_step, min_step,
-                                 max_num_steps, maxl, QMAX);
+                                 max_num_steps, maxl, max_order);
     }
     if (problem == 1)
         return oracle_ode_create(3, robertson_rhs, NULL, t0, y0, rtol, atol, init_step, max_step, min_step,
-                                 max_num_steps, maxl, QMAX);
+                                 max_num_steps, maxl, max_order);
     if (problem == 2)
         return oracle_ode_create(3, decay_rhs, (void *)DECAY_LAMBDA, t0, y0, rtol, atol, init_step, max_step,
-                                 min_step, max_num_steps, maxl, QMAX);
+                                 min_step, max_num_steps, maxl, max_order);
     return NULL;
 }

@@ -86,6 +86,92 @@ def test_device_integrator_bit_identical(kat, device_order, problem, n, rtol, at
     kat.shud_kat_ode_free(u)
 
 
+N_DECAYN = 7 * 300 + 37          # three reduction blocks, ragged tail
+
+
+@pytest.mark.parametrize("maxl,touts", [(2, [0.01, 1.0]), (3, [0.01, 1.0, 10.0]), (32, [0.01, 1.0, 10.0])])
+def test_device_integrator_krylov_dimension(kat, device_order, maxl, touts):
+    """ShudOdeOptions.maxl.  With maxl 2 and 3 SPGMR runs out of Krylov vectors on decayn (seven rates over six
+    decades): the linear-convergence-failure path (ncfl) and the Newton-convergence-failure path (restore + rescale
+    by 0.25; ncfn) are really taken — the default maxl has ncfl == ncfn == 0 on every test problem.  maxl 32 only
+    changes the slab layout and must reproduce the default run's counters."""
+    n = N_DECAYN
+    y0 = 1.0 + 0.5 * np.sin(np.arange(n))
+    u, fn = _dev(kat, "decayn", n)
+    d = rt.OdeSolver(None, 0.0, y0, 1e-6, 1e-10, 1e-5, 0.0, 0.0, maxl=maxl, fn=fn)
+    o = oracle.OracleOde("decayn", 0.0, y0, 1e-6, 1e-10, 1e-5, 0.0, 0.0, maxl=maxl)
+    for tout in touts:
+        fd, td, yd = d.solve(tout)
+        fo, to, yo = o.solve(tout)
+        assert fd == fo == 0 and td == to == tout
+        assert np.array_equal(yd, yo), (tout, np.abs(yd - yo).max())
+    sd, so = d.stats(), o.stats()
+    _same_stats(sd, so)
+    if maxl < 5:
+        assert so["ncfl"] > 0 and so["ncfn"] > 0, so
+    else:
+        o5 = oracle.OracleOde("decayn", 0.0, y0, 1e-6, 1e-10, 1e-5, 0.0, 0.0)
+        for tout in touts:
+            o5.solve(tout)
+        _same_stats(sd, o5.stats())
+    d.close()
+    kat.shud_kat_ode_free(u)
+
+
+@pytest.mark.parametrize("problem,max_order,rtol,atol,h0,touts", [
+    # (tolerances per order so that every case stays below ~2000 steps: a low order needs small steps)
+    ("robertson", 1, 1e-4, 1e-9, 1e-6, [0.4, 4.0, 40.0]),
+    ("robertson", 2, 1e-6, 1e-12, 1e-6, [0.4, 4.0, 40.0]),
+    ("robertson", 3, 1e-6, 1e-12, 1e-6, [0.4, 4.0, 40.0]),
+    ("decayn", 1, 1e-3, 1e-6, 1e-5, [0.01, 1.0, 10.0]),
+    ("decayn", 2, 1e-5, 1e-9, 1e-5, [0.01, 1.0, 10.0]),
+    ("decayn", 3, 1e-6, 1e-10, 1e-5, [0.01, 1.0, 10.0]),
+])
+def test_device_integrator_max_order(kat, device_order, problem, max_order, rtol, atol, h0, touts):
+    """ShudOdeOptions.max_order (CVodeSetMaxOrd): the zn slab has max_order + 1 columns, acor is saved into
+    zn[max_order], and every q != qmax branch sits at a lower order."""
+    n = 3 if problem == "robertson" else N_DECAYN
+    y0 = np.array([1.0, 0.0, 0.0]) if problem == "robertson" else 1.0 + 0.5 * np.sin(np.arange(n))
+    u, fn = _dev(kat, problem, n)
+    d = rt.OdeSolver(None, 0.0, y0, rtol, atol, h0, 0.0, 0.0, max_order=max_order, fn=fn)
+    o = oracle.OracleOde(problem, 0.0, y0, rtol, atol, h0, 0.0, 0.0, max_order=max_order)
+    for tout in touts:
+        fd, td, yd = d.solve(tout)
+        fo, to, yo = o.solve(tout)
+        assert fd == fo == 0 and td == to == tout
+        assert np.array_equal(yd, yo), (tout, np.abs(yd - yo).max())
+        sd = d.stats()
+        assert sd["qcur"] <= max_order and sd["qlast"] <= max_order
+        for k in range(max_order + 1):
+            for tt in [sd["tcur"], sd["tcur"] - 0.3 * sd["hlast"]]:
+                (fdk, dd), (fok, do) = d.get_dky(tt, k), o.get_dky(tt, k)
+                assert fdk == fok, (k, tt, fdk, fok)
+                if fdk == 0:
+                    assert np.array_equal(dd, do), (k, tt)
+    _same_stats(d.stats(), o.stats())
+    assert d.stats()["qcur"] == max_order            # (the limit binds: the unrestricted runs reach higher orders)
+    d.close()
+    kat.shud_kat_ode_free(u)
+
+
+def test_device_integrator_large_n_finalize_second_trip(kat, device_order):
+    """decayn at n = 4096*1024 + 1061: 4098 partials, so every reduction of a real controller loop takes the
+    finalize's second trip with guarded loads.  Six one-step solves, the state bit-identical after each."""
+    n = 4096 * 1024 + 1061
+    u, fn = _dev(kat, "decayn", n)
+    y0 = 1.0 + 0.5 * np.sin(np.arange(n))
+    d = rt.OdeSolver(None, 0.0, y0, 1e-6, 1e-10, 1e-5, 0.0, 0.0, fn=fn)
+    o = oracle.OracleOde("decayn", 0.0, y0, 1e-6, 1e-10, 1e-5, 0.0, 0.0)
+    for k in range(6):
+        fd, td, yd = d.solve(1.0, one_step=True)
+        fo, to, yo = o.solve(1.0, one_step=True)
+        assert fd == fo == 0 and td == to
+        assert np.array_equal(yd, yo), (k, np.abs(yd - yo).max())
+    _same_stats(d.stats(), o.stats())
+    d.close()
+    kat.shud_kat_ode_free(u)
+
+
 def test_device_stop_time_one_step_dky(kat, device_order):
     u, fn = _dev(kat, "decay", 3)
     y0 = np.ones(3)

@@ -67,17 +67,20 @@ def test_run_to_run_determinism(n, seed, mode):
         assert np.array_equal(d0[k], d1[k], equal_nan=True), k
 
 
-# the CPU restatement integrates sequentially: sizes just past the 2048-block reduction grid exercise the
-# grid-stride tail without spending minutes in the oracle (12 examples up to 2600 blocks took 133 s, 8 up to 2100
-# blocks 83 s; 5 keep both size bands under derandomize)
+# the CPU restatement integrates sequentially, so the sizes stay small (12 examples up to 2600 blocks of 256 took
+# 133 s, 8 up to 2100 blocks 83 s; 5 keep both size bands under derandomize).  The bands date from a 2048-block
+# grid-stride reduction grid of 256-thread blocks that no longer exists: on today's one-shot grid of 1024-thread
+# reduction blocks they are 1..76 and 511..526 partials, all inside the finalize's first regime (acc[0] only).  The
+# finalize's other regimes (more than 1024 and more than 4096 partials) are covered per kernel in
+# tests/test_gpu_ode_kernels.py and inside a controller loop in tests/test_gpu_ode.py.
 @settings(max_examples=5, deadline=None, derandomize=True,
           suppress_health_check=[HealthCheck.too_slow, HealthCheck.function_scoped_fixture])
 @given(blocks=st.one_of(st.integers(0, 300), st.integers(2044, 2100)), tail=st.integers(1, 255),
        rtol_e=st.integers(4, 8), atol_e=st.integers(8, 12), h0_e=st.integers(2, 6))
 def test_integrator_random_sizes_bit_identical(blocks, tail, rtol_e, atol_e, h0_e):
-    """decayn with n = 256*blocks + tail: the reduction grid (min(ceil(n/256), 2048) blocks, grid-stride:
-    above 2048 blocks each thread sums several entries) and the element-wise grid (one entry per thread) both
-    see partial blocks and odd tails."""
+    """decayn with n = 256*blocks + tail: the reduction grid (ceil(n/1024) blocks of 1024 threads, one entry per
+    thread, at most 526 partials here) and the element-wise grid (ceil(n/256) blocks of 256 threads, one entry per
+    thread) both see partial blocks and odd tails."""
     import ctypes as C
     import os
 
