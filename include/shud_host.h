@@ -79,6 +79,11 @@ int shud_project_outputs(shud_project_t p, const char *outdir, ShudOutputDecl *d
 /* output interval [min] of the water-balance diagnostics (include/shud_wb.h): dt_qe_ET if positive, else
  * dt_ye_SURF if positive, else 1440 (choose_interval_min, src/Model/WaterBalanceDiag.cpp:10-19); -1 for NULL */
 int shud_project_wb_interval(shud_project_t p);
+/* CS.UpdateICStep [min]: Update_IC_STEP of <prj>.cfg.para (Model_Control.cpp:189; default 1440,
+ * Model_Control.hpp:181), the schedule of the .cfg.ic.update snapshots (include/shud_mon.h); -1 for NULL */
+int shud_project_update_ic_step(shud_project_t p);
+/* Riv[i].type of <prj>.sp.riv, 1-based as in the file (the Type column of <prj>.flood.csv); n = NumRiv */
+const int32_t *shud_project_riv_type(shud_project_t p, int64_t *n);
 
 /* Per ET step [t, tout): updateAllTimeSeries(t) (movePointer of every forcing / LAI / MF series) and the
  * inputs of tReadForcing + ET for shud_et_step: the current station rows, LAI and MF rows, and the TSR

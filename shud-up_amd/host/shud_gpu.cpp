@@ -1,7 +1,7 @@
 // shud_gpu.cpp — C++ host of the device path: SHUD() (src/Model/shud.cpp:32-170) with the RHS, the ET-step
 // prelude, the integrator and the outputs on one MI355X, driven through the C-ABIs of include/.
 //
-//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] <input_dir> <project>
+//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] <input_dir> <project>
 //   shud_gpu --rhs-check K | --rhs-bench [--evals N] ...   partitioned RHS modes (shud_gpu_part.cpp)
 //
 // input_dir/<project>.* are the reference's input files (FileIn, IO.cpp:53-91); forcing csv paths in
@@ -26,8 +26,16 @@
 // the carried state, so the trajectory differs from a run without QUAD, as in the reference.  Without
 // SHUD_WB_DIAG the loop makes exactly the calls it made before, and without SHUD_WB_DIAG_QUAD exactly those of
 // SHUD_WB_DIAG alone.
-// Not restated (out of the device path's scope): flood alerts, the screen print / .cfg.ic.update snapshots,
-// NetCDF forcing and outputs, the uncoupled -g mode.
+// --flood and --ic-snapshots run the reference's run monitors on the device (include/shud_mon.h).  The reference
+// always writes their files; here both are off by default, and without the flags the loop makes exactly the calls
+// it made before.  --ic-snapshots: <prj>.cfg.ic.bak before the loop with header time 0 (shud.cpp:76),
+// PrintInit(Init_update, t) at the top of every solver step (shud.cpp:97) and once after the loop (shud.cpp:157).
+// The .bak file and any snapshot taken before the first step come from LoadIC's host arrays: the pre-loop
+// shud_rhs_summary has already put boundary heads into the device arrays, which the reference's arrays do not hold
+// at that point.  --flood: FloodWarning(t) after ExportResults (shud.cpp:154) on the arrays summary and the
+// diagnostics replay have just filled, into <prj>.flood.csv.
+// Not restated (out of the device path's scope): the screen print, NetCDF forcing and outputs, the uncoupled -g
+// mode.
 #include <strings.h>
 #include <sys/stat.h>
 
@@ -37,10 +45,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "shud_et.h"
 #include "shud_host.h"
+#include "shud_mon.h"
 #include "shud_ode.h"
 #include "shud_out.h"
 #include "shud_rhs.h"
@@ -49,8 +59,13 @@
 static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 
 static void usage() {
-    fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] <input_dir> <project>\n"
-                    "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n");
+    fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots]\n"
+                    "                <input_dir> <project>\n"
+                    "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n"
+                    "  --flood         write <outdir>/<project>.flood.csv (reaches above their bank after each solver step)\n"
+                    "  --ic-snapshots  write <outdir>/<project>.cfg.ic.bak and, every Update_IC_STEP minutes and at the\n"
+                    "                  end, <outdir>/<project>.cfg.ic.update (restart file for INIT_MODE 3)\n"
+                    "  Both are off by default (the reference always writes these files).\n");
 }
 
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
@@ -85,7 +100,7 @@ int main(int argc, char **argv) {
     long long max_steps = -1;
     bool quiet = false;
     int rhs_check = 0, evals = 0;
-    bool rhs_bench = false;
+    bool rhs_bench = false, want_flood = false, want_ic = false;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -96,6 +111,8 @@ int main(int argc, char **argv) {
         else if (a == "-q") quiet = true;
         else if (a == "--rhs-check" && i + 1 < argc) rhs_check = atoi(argv[++i]);
         else if (a == "--rhs-bench") rhs_bench = true;
+        else if (a == "--flood") want_flood = true;
+        else if (a == "--ic-snapshots") want_ic = true;
         else if (a == "--evals" && i + 1 < argc) evals = atoi(argv[++i]);
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else pos.push_back(argv[i]);
@@ -222,6 +239,76 @@ int main(int argc, char **argv) {
         }
     }
 
+    // ---- PrintInit(Init_bak, 0) and InitFloodAlert (shud.cpp:76-77), only with --ic-snapshots / --flood ----
+    shud_mon_t mon = nullptr;
+    const std::string ic_update = outdir + "/" + prj + ".cfg.ic.update";
+    const int NE = mesh.num_ele, NR = mesh.num_riv, NL = mesh.num_lake;
+    // LoadIC's values through the device-free formatter (what the reference's arrays hold before the first step)
+    auto ic_from_host = [&](const std::string &fn, double th) {
+        return shud_mon_write_ic_host(fn.c_str(), th, NE, NR, NL, y_is, y_snow, y0, y0 + NE, y0 + 2 * (size_t)NE,
+                                      y0 + 3 * (size_t)NE, NL ? y0 + 3 * (size_t)NE + NR : nullptr);
+    };
+    long long ic_snaps = 0;
+    if (want_flood || want_ic) {
+        if (shud_mon_create(0, shud_rhs_stream(h), &mon)) {
+            fprintf(stderr, "shud_mon_create: %s\n", shud_rhs_last_error_string());
+            return 1;
+        }
+        if (want_ic) {
+            const std::string bak = outdir + "/" + prj + ".cfg.ic.bak";
+            if (ic_from_host(bak, 0)) {
+                fprintf(stderr, "cannot write %s\n", bak.c_str());
+                return 1;
+            }
+            ShudIcSpec is = {ic_update.c_str(), shud_project_update_ic_step(p), NE, NR, NL,
+                             shud_rhs_device_array(h, SHUD_ARR_Y_ELE_IS, nullptr),
+                             shud_rhs_device_array(h, SHUD_ARR_Y_ELE_SNOW, nullptr),
+                             shud_rhs_device_array(h, SHUD_ARR_Y_ELE_SURF, nullptr),
+                             shud_rhs_device_array(h, SHUD_ARR_Y_ELE_UNSAT, nullptr),
+                             shud_rhs_device_array(h, SHUD_ARR_Y_ELE_GW, nullptr),
+                             shud_rhs_device_array(h, SHUD_ARR_Y_RIV_STG, nullptr),
+                             NL ? shud_rhs_device_array(h, SHUD_ARR_Y_LAKE_STG, nullptr) : nullptr};
+            if (shud_mon_add_ic(mon, &is)) {
+                fprintf(stderr, "shud_mon_add_ic: %s\n", shud_rhs_last_error_string());
+                return 1;
+            }
+        }
+        if (want_flood) {
+            const std::string fcsv = outdir + "/" + prj + ".flood.csv";
+            ShudFloodSpec fs = {fcsv.c_str(), shud_rhs_device_array(h, SHUD_ARR_Y_RIV_STG, nullptr),
+                                shud_rhs_device_array(h, SHUD_ARR_QRIV_DOWN, nullptr), NR, mesh.riv_depth,
+                                shud_project_riv_type(p, nullptr)};
+            if (shud_mon_add_flood(mon, &fs)) {
+                fprintf(stderr, "shud_mon_add_flood: %s\n", shud_rhs_last_error_string());
+                return 1;
+            }
+        }
+    }
+    // PrintInit(Init_update, t): LoadIC's values until the first step has run (formatted on a thread of its own,
+    // joined before anything else may write the file), the device arrays afterwards
+    std::thread ic0;
+    int ic0_rc = 0;
+    auto ic0_join = [&]() {
+        if (ic0.joinable()) ic0.join();
+        return ic0_rc;
+    };
+    auto ic_update_at = [&](double tt, bool stepped) {
+        int due = ic0_join() ? -1 : 0;
+        if (due == 0 && stepped) {
+            due = shud_mon_ic_update(mon, tt);
+        } else if (due == 0) {
+            const int ustep = shud_project_update_ic_step(p);
+            due = ((unsigned long)(long)tt) % (unsigned long)ustep == 0;
+            if (due) ic0 = std::thread([&ic0_rc, &ic_from_host, &ic_update, tt] { ic0_rc = ic_from_host(ic_update, tt); });
+        }
+        if (due < 0) {
+            fprintf(stderr, "restart snapshot at t = %f: %s\n", tt, shud_rhs_last_error_string());
+            return 1;
+        }
+        ic_snaps += due;
+        return 0;
+    };
+
     // ---- the time loop (shud.cpp:86-140) ----
     shud_rhs_synchronize(h);
     const auto loop0 = std::chrono::steady_clock::now();
@@ -231,7 +318,8 @@ int main(int argc, char **argv) {
     int rc = 0;
     // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
     // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag, quad monitor (its f(), replay and pass)
-    double ph[7] = {0, 0, 0, 0, 0, 0, 0};
+    // run monitors (their enqueue; the writer thread's own time is reported beside it)
+    double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto tick = std::chrono::steady_clock::now();
     auto lap = [&](int k) {
         const auto now = std::chrono::steady_clock::now();
@@ -239,6 +327,13 @@ int main(int argc, char **argv) {
         tick = now;
     };
     for (long long i = 0; i < nsteps && !rc; i++) {
+        if (want_ic) {                            // MD->PrintInit(fout->Init_update, t)
+            if (ic_update_at(t, i > 0)) {
+                rc = 1;
+                break;
+            }
+            lap(7);
+        }
         tnext += c.solver_step;
         while (t + kZero < tnext) {
             const double tout = et_sub ? std::fmin(t + c.et_step, tnext) : tnext;
@@ -335,11 +430,41 @@ int main(int argc, char **argv) {
             rc = 1;
         }
         lap(4);
+        if (want_flood) {                         // MD->flood->FloodWarning(t)
+            if (shud_mon_flood(mon, t)) {
+                fprintf(stderr, "shud_mon_flood: %s\n", shud_rhs_last_error_string());
+                rc = 1;
+            }
+            lap(7);
+        }
         if (!quiet && c.verbose) printf("step %lld  t = %.3f min\n", i + 1, t);
+    }
+    if (want_ic && !rc) {                         // MD->PrintInit(fout->Init_update, t) after the loop
+        if (ic_update_at(t, nsteps > 0)) rc = 1;
+        lap(7);
     }
     shud_rhs_synchronize(h);
     const double loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop0).count();
     shud_out_destroy(out);
+    long long flood_rows = 0;
+    double mon_writer_s = 0.0;
+    if (mon) {
+        if (ic0_join()) {
+            fprintf(stderr, "cannot write %s\n", ic_update.c_str());
+            if (!rc) rc = 1;
+        }
+        if (shud_mon_flush(mon)) {
+            fprintf(stderr, "shud_mon_flush: %s\n", shud_rhs_last_error_string());
+            if (!rc) rc = 1;
+        } else {
+            if (want_flood) flood_rows = (long long)shud_mon_flood_rows(mon);
+            mon_writer_s = shud_mon_writer_seconds(mon);
+        }
+        if (shud_mon_destroy(mon)) {
+            fprintf(stderr, "shud_mon_destroy: %s\n", shud_rhs_last_error_string());
+            if (!rc) rc = 1;
+        }
+    }
     if (wb && shud_wb_destroy(wb)) {
         fprintf(stderr, "shud_wb_destroy: %s\n", shud_rhs_last_error_string());
         if (!rc) rc = 1;
@@ -353,8 +478,13 @@ int main(int argc, char **argv) {
                t, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni, (long long)st.nli,
                (long long)st.netf, nprint, wall, loop_s);
     // one machine-readable line (tools/e2e.sh); the quad monitor's phase and step count appear only
-    // when it ran
-    char quad_txt[48] = "", quad_n[48] = "";
+    // when it ran, and so do the run monitors' phase, writer time and counts
+    char quad_txt[48] = "", quad_n[48] = "", mon_txt[48] = "", mon_n[128] = "";
+    if (mon) {
+        snprintf(mon_txt, sizeof(mon_txt), ", \"monitors\": %.4f", ph[7]);
+        snprintf(mon_n, sizeof(mon_n), "\"flood_rows\": %lld, \"ic_snapshots\": %lld, \"monitors_writer_s\": %.4f, ",
+                 flood_rows, ic_snaps, mon_writer_s);
+    }
     if (quad) {
         snprintf(quad_txt, sizeof(quad_txt), ", \"wb_quad\": %.4f", ph[6]);
         snprintf(quad_n, sizeof(quad_n), "\"quad_steps\": %lld, ", quad_steps);
@@ -362,11 +492,11 @@ int main(int argc, char **argv) {
     printf("{\"shud_gpu\": {\"num_ele\": %d, \"t_end_min\": %.6f, \"solver_steps\": %lld, \"cvode_steps\": %lld, "
            "\"rhs_evals\": %lld, \"newton_iters\": %lld, \"krylov_iters\": %lld, \"outputs\": %d, "
            "\"wall_s\": %.4f, \"loop_s\": %.4f, \"loop_phases_s\": {\"forcing\": %.4f, \"et_step\": %.4f, "
-           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f%s}, \"host_syncs\": %lld, "
-           "%s\"exit\": %d}}\n",
+           "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f%s%s}, \"host_syncs\": %lld, "
+           "%s%s\"exit\": %d}}\n",
            mesh.num_ele, t, nsteps, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni,
-           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], quad_txt,
-           (long long)st.n_sync, quad_n, rc);
+           (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], quad_txt, mon_txt,
+           (long long)st.n_sync, quad_n, mon_n, rc);
     shud_ode_destroy(ode);
     shud_rhs_device_free(h, d_y);
     if (d_du) shud_rhs_device_free(h, d_du);

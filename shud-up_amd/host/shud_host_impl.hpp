@@ -45,6 +45,8 @@ struct Project {
     std::map<std::string, double> cal;           // globalCal keys (upper case) -> value, defaults applied
     double fz_sub_max = -3, fz_sub_min = -10, fz_sub_day = 28, fz_surf_max = -1, fz_surf_min = -5, fz_surf_day = 7;
     double solar_lon_fixed = -9999.0, solar_lat_fixed = -9999.0;
+    int update_ic_step = 1440;                   // UpdateICStep (Model_Control.hpp:181)
+    std::vector<int32_t> riv_type;               // Riv[i].type, 1-based
 
     int NE = 0, NR = 0, NS = 0, NL = 0, NumNode = 0, NumLC = 0;
     // mesh SoA (ShudMeshSoA), params (ShudParamsSoA), ET statics (ShudEtMeshSoA)

@@ -137,6 +137,7 @@ static int read_para(Project &p, double end_day) {
         else if (is("VERBOSE")) c.verbose = (int)val;
         else if (is("CloseBoundary")) c.close_boundary = (int)val;
         else if (is("INIT_MODE")) c.init_type = (int)val;
+        else if (is("Update_IC_STEP")) p.update_ic_step = (int)val;
         else if (is("ABSTOL")) c.abstol = val;
         else if (is("RELTOL")) c.reltol = val;
         else if (is("INIT_SOLVER_STEP")) c.init_step = val;
@@ -416,7 +417,7 @@ int load(Project &p, const char *indir, const char *prj, const char *cwd, double
     // ---- rivers: initialRiver/applyParameter, BedSlope >= MINRIVSLOPE, updateFrDownstream, segments ----
     p.riv_down.resize(NR); p.riv_bc.resize(NR); p.riv_length.resize(NR); p.riv_slope.resize(NR);
     p.riv_d2d.resize(NR); p.riv_avg_rough.resize(NR); p.riv_depth.resize(NR); p.riv_bw.resize(NR);
-    p.riv_bs.resize(NR); p.riv_ksath.resize(NR); p.riv_bedthick.resize(NR);
+    p.riv_bs.resize(NR); p.riv_ksath.resize(NR); p.riv_bedthick.resize(NR); p.riv_type.resize(NR);
     std::vector<double> rrough(NR);
     std::vector<int> rt(NR);
     for (int r = 0; r < NR; r++) {
@@ -424,6 +425,7 @@ int load(Project &p, const char *indir, const char *prj, const char *cwd, double
         if (down == 0) return fail(&p, "river reach %d with down == 0: the reference exits (MD_RiverFlux.cpp:55-57)", r + 1);
         rt[r] = (int)riv.at(r, 2) - 1;
         if (rt[r] < 0 || rt[r] >= nrt) return fail(&p, "river reach %d: type out of range", r + 1);
+        p.riv_type[r] = rt[r] + 1;
         p.riv_down[r] = down > 0 ? down - 1 : down;
         p.riv_bc[r] = (int32_t)riv.at(r, 5);
         p.riv_length[r] = riv.at(r, 4);
@@ -568,6 +570,18 @@ int shud_project_wb_interval(shud_project_t h) {
     if (p.dt_qe_et > 0) return p.dt_qe_et;
     if (p.dt_ye_surf > 0) return p.dt_ye_surf;
     return 1440;
+}
+
+int shud_project_update_ic_step(shud_project_t h) {
+    return h ? reinterpret_cast<Project *>(h)->update_ic_step : -1;
+}
+
+const int32_t *shud_project_riv_type(shud_project_t h, int64_t *n) {
+    if (n) *n = 0;
+    if (!h) return nullptr;
+    const Project &p = *reinterpret_cast<Project *>(h);
+    if (n) *n = (int64_t)p.riv_type.size();
+    return p.riv_type.data();
 }
 
 int shud_project_mesh(shud_project_t h, ShudMeshSoA *m, ShudParamsSoA *q) {

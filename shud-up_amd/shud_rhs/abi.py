@@ -286,10 +286,47 @@ WB_FUNCTIONS = {
 }
 
 
+# ---- include/shud_mon.h (run monitors on the device: flood alerts and restart snapshots) ----
+SHUD_MON_ERR_IO = -6
+
+
+class ShudFloodSpec(C.Structure):
+    _fields_ = [("path", C.c_char_p), ("d_stage", C.c_void_p), ("d_qdown", C.c_void_p), ("n_riv", C.c_int32),
+                ("riv_depth", c_double_p), ("riv_type", c_int32_p)]
+
+
+class ShudIcSpec(C.Structure):
+    _fields_ = [("path_update", C.c_char_p), ("update_ic_step", C.c_int32), ("n_ele", C.c_int32),
+                ("n_riv", C.c_int32), ("n_lake", C.c_int32), ("d_is", C.c_void_p), ("d_snow", C.c_void_p),
+                ("d_surf", C.c_void_p), ("d_unsat", C.c_void_p), ("d_gw", C.c_void_p), ("d_riv", C.c_void_p),
+                ("d_lake", C.c_void_p)]
+
+
+MON_FUNCTIONS = {
+    "shud_mon_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "shud_mon_add_flood": (C.c_int, [_H, C.POINTER(ShudFloodSpec)]),
+    "shud_mon_flood": (C.c_int, [_H, C.c_double]),
+    "shud_mon_flood_rows": (C.c_int64, [_H]),
+    "shud_mon_flood_last": (C.c_int, [_H]),
+    "shud_mon_add_ic": (C.c_int, [_H, C.POINTER(ShudIcSpec)]),
+    "shud_mon_ic_update": (C.c_int, [_H, C.c_double]),
+    "shud_mon_ic_snapshots": (C.c_int64, [_H]),
+    "shud_mon_flush": (C.c_int, [_H]),
+    "shud_mon_writer_seconds": (C.c_double, [_H]),
+    "shud_mon_destroy": (C.c_int, [_H]),
+    "shud_mon_time_flood": (C.c_int, [_H, C.c_int, c_double_p]),
+    "shud_mon_write_ic_host": (C.c_int, [C.c_char_p, C.c_double, C.c_int32, C.c_int32, C.c_int32] + [c_double_p] * 7),
+    "shud_mon_flood_header": (C.c_char_p, []),
+    "shud_mon_format_flood_rows": (C.c_int64, [C.c_char_p, C.c_int64, C.c_double, c_int32_p, c_int32_p, c_double_p,
+                                               c_double_p, c_double_p, C.c_int64]),
+}
+
+
 def bind(lib, strict=True):
     """set the signatures; strict=False (A/B builds of older sources) skips symbols the library lacks"""
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
-                              + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())):
+                              + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())
+                              + list(MON_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

@@ -55,6 +55,8 @@ def lib():
             "shud_project_array": (C.POINTER(C.c_double), [_H, C.c_char_p, C.POINTER(C.c_int64)]),
             "shud_project_outputs": (C.c_int, [_H, C.c_char_p, C.POINTER(ShudOutputDecl), C.c_int]),
             "shud_project_wb_interval": (C.c_int, [_H]),
+            "shud_project_update_ic_step": (C.c_int, [_H]),
+            "shud_project_riv_type": (C.POINTER(C.c_int32), [_H, C.POINTER(C.c_int64)]),
             "shud_project_forcing": (C.c_int, [_H, C.c_double, C.c_double, C.POINTER(abi.ShudEtForcing)]),
             "shud_project_bc_rows": (C.c_int, [_H, C.POINTER(abi.ShudStepInputs)]),
             "shud_project_solar": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -155,6 +157,17 @@ class Project:
     def wb_interval(self):
         """output interval [min] of the water-balance diagnostics: dt_qe_ET, else dt_ye_SURF, else 1440"""
         return lib().shud_project_wb_interval(self.h)
+
+    def update_ic_step(self):
+        """Update_IC_STEP [min] of .cfg.para (default 1440): the schedule of the .cfg.ic.update snapshots"""
+        return lib().shud_project_update_ic_step(self.h)
+
+    def riv_type(self):
+        """Riv[i].type of .sp.riv, 1-based (the Type column of .flood.csv)"""
+        n = C.c_int64()
+        p = lib().shud_project_riv_type(self.h, C.byref(n))
+        a = _arr(p, n.value, np.int32)
+        return np.zeros(0, dtype=np.int32) if a is None else a
 
     def bc_rows(self):
         """{ele_ybc, ele_qbc, riv_ybc, riv_qbc} rows at the current ET step (model.step_struct bc_tables form:

@@ -482,3 +482,125 @@ class WaterBalance:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def _dptr(x):
+    """device address of a torch tensor (data_ptr) or a raw pointer (int / None)"""
+    if x is None:
+        return None
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+
+
+class RunMonitors:
+    """The reference's run monitors on the device (include/shud_mon.h): add_flood + flood(t) =
+    FloodAlert::Init* + FloodWarning(t) into <prj>.flood.csv, add_ic + ic_update(t) = PrintInit(Init_update, t)
+    into <prj>.cfg.ic.update.  Independent of the RHS handle: device arrays are torch tensors (float64, contiguous,
+    kept alive by the caller) or raw device pointers; rows and snapshots reach the files asynchronously (flush)."""
+
+    def __init__(self, device=0, stream=None):
+        h = C.c_void_p()
+        _check(lib().shud_mon_create(int(device), None if stream is None else C.c_void_p(stream), C.byref(h)),
+               "shud_mon_create")
+        self.h = h
+        self._keep = []
+
+    def add_flood(self, path, d_stage, d_qdown, n_riv, riv_depth, riv_type):
+        depth = np.ascontiguousarray(riv_depth, dtype=np.float64)
+        typ = np.ascontiguousarray(riv_type, dtype=np.int32)
+        assert depth.size == typ.size == int(n_riv)
+        pth = str(path).encode()
+        spec = abi.ShudFloodSpec(pth, _dptr(d_stage), _dptr(d_qdown), int(n_riv),
+                                 depth.ctypes.data_as(abi.c_double_p), typ.ctypes.data_as(abi.c_int32_p))
+        self._keep.append((pth, d_stage, d_qdown))
+        _check(lib().shud_mon_add_flood(self.h, C.byref(spec)), "shud_mon_add_flood")
+
+    def flood(self, t):
+        _check(lib().shud_mon_flood(self.h, float(t)), "shud_mon_flood")
+
+    def flood_rows(self):
+        """total rows written (waits for the writer)"""
+        n = lib().shud_mon_flood_rows(self.h)
+        if n < 0:
+            _check(int(n), "shud_mon_flood_rows")
+        return n
+
+    def flood_last(self):
+        """FloodWarning's return value for the last flood() call (waits for the writer)"""
+        rc = lib().shud_mon_flood_last(self.h)
+        if rc < 0:
+            _check(rc, "shud_mon_flood_last")
+        return rc
+
+    def add_ic(self, path_update, update_ic_step, d_is, d_snow, d_surf, d_unsat, d_gw, d_riv, d_lake, n_ele, n_riv,
+               n_lake=0):
+        pth = str(path_update).encode()
+        arrs = (d_is, d_snow, d_surf, d_unsat, d_gw, d_riv, d_lake if n_lake else None)
+        spec = abi.ShudIcSpec(pth, int(update_ic_step), int(n_ele), int(n_riv), int(n_lake), *[_dptr(a) for a in arrs])
+        self._keep.append((pth,) + arrs)
+        _check(lib().shud_mon_add_ic(self.h, C.byref(spec)), "shud_mon_add_ic")
+
+    def ic_update(self, t):
+        """True when a snapshot was due and queued"""
+        rc = lib().shud_mon_ic_update(self.h, float(t))
+        if rc < 0:
+            _check(rc, "shud_mon_ic_update")
+        return rc == 1
+
+    def ic_snapshots(self):
+        n = lib().shud_mon_ic_snapshots(self.h)
+        if n < 0:
+            _check(int(n), "shud_mon_ic_snapshots")
+        return n
+
+    def flush(self):
+        """wait until every queued row and snapshot is in its file; raises on the writer's first failure"""
+        _check(lib().shud_mon_flush(self.h), "shud_mon_flush")
+
+    def writer_seconds(self):
+        return lib().shud_mon_writer_seconds(self.h)
+
+    def time_flood(self, reps):
+        """milliseconds per flood pass over `reps` passes (HIP events; shud_mon_time_flood)"""
+        ms = C.c_double()
+        _check(lib().shud_mon_time_flood(self.h, int(reps), C.byref(ms)), "shud_mon_time_flood")
+        return ms.value
+
+    def close(self):
+        """shud_mon_destroy; raises if the asynchronous writer failed"""
+        if self.h:
+            rc = lib().shud_mon_destroy(self.h)
+            self.h = None
+            _check(rc, "shud_mon_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def write_ic_host(path, t, y_is, y_snow, y_surf, y_unsat, y_gw, y_riv, y_lake=None):
+    """PrintInit's file from host arrays (shud_mon_write_ic_host): the .cfg.ic layout, through <path>.tmp + rename"""
+    a = [np.ascontiguousarray(v, dtype=np.float64) for v in (y_is, y_snow, y_surf, y_unsat, y_gw, y_riv)]
+    lake = None if y_lake is None or len(y_lake) == 0 else np.ascontiguousarray(y_lake, dtype=np.float64)
+    ne, nr, nl = a[0].size, a[5].size, 0 if lake is None else lake.size
+    assert all(v.size == ne for v in a[:5])
+    ptr = [v.ctypes.data_as(abi.c_double_p) for v in a] + [None if lake is None else lake.ctypes.data_as(abi.c_double_p)]
+    _check(lib().shud_mon_write_ic_host(str(path).encode(), float(t), ne, nr, nl, *ptr), "shud_mon_write_ic_host")
+
+
+def format_flood_rows(t, idx, riv_type, stage, riv_depth, q):
+    """FloodWarning's rows (bytes) for packed records: record k is reach idx[k] (0-based) with stage[k], q[k];
+    riv_type / riv_depth are per-reach arrays (shud_mon_format_flood_rows)"""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    typ = np.ascontiguousarray(riv_type, dtype=np.int32)
+    st, dp, qq = (np.ascontiguousarray(v, dtype=np.float64) for v in (stage, riv_depth, q))
+    args = (float(t), idx.ctypes.data_as(abi.c_int32_p), typ.ctypes.data_as(abi.c_int32_p),
+            st.ctypes.data_as(abi.c_double_p), dp.ctypes.data_as(abi.c_double_p), qq.ctypes.data_as(abi.c_double_p),
+            int(idx.size))
+    n = lib().shud_mon_format_flood_rows(None, 0, *args)
+    if n < 0:
+        _check(int(n), "shud_mon_format_flood_rows")
+    buf = C.create_string_buffer(n + 1)
+    lib().shud_mon_format_flood_rows(buf, n + 1, *args)
+    return buf.raw[:n]
