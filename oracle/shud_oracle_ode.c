@@ -152,7 +152,8 @@ static void v_linear_sum(long n, double a, const double *x, double b, const doub
 }
 
 /* Reduction order.  0: the serial N_Vector's (one left-to-right sum, nvector_serial.c) — CVODE's own order.
- * 1: the device integrator's fixed order (shud-up_amd/csrc/shud_ode_kernels.hip, round 3): one entry per thread on
+ * 1: the device's fixed order (shud-up_amd/csrc/shud_reduce.h, the one reduction the integrator's kernels and the
+ * water-balance diagnostics share; round 3): one entry per thread on
  * a grid of B = ceil(n/1024) blocks x 1024 threads; thread (b, t) holds 0.0 + term[b*1024 + t] (0.0 past n); each
  * 64-lane wave combines by an xor butterfly (offsets 32..1, own value first) and lane 0 keeps the result; the block
  * combines its 16 wave results by an xor butterfly over offsets 8..1 (lane 0) into partial[b].  The one-block finalize (1024 threads): thread t keeps 4
@@ -161,7 +162,7 @@ static void v_linear_sum(long n, double a, const double *x, double b, const doub
  * device integrator bit for bit wherever the RHS is IEEE-exact (tests/test_gpu_ode.py).  (Round 2's order — a
  * 2048-block grid-stride loop of 256-thread blocks — ran the five-operand passes at 4.7 TB/s against 5.7 TB/s
  * one-shot: profiles/r03/ode/.) */
-#define ORACLE_RED_THREADS 1024   /* shud_ode_dev.h kRedThreads */
+#define ORACLE_RED_THREADS 1024   /* shud_reduce.h kRedThreads */
 #define ORACLE_FIN_THREADS 1024   /* kFinThreads */
 #define ORACLE_FIN_ACC 4          /* kFinAcc */
 static int g_red_order = 0;

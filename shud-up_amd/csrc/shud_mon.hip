@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "shud_diag_host.h"
 #include "shud_handle.h"
 #include "shud_mon.h"
 #include "shud_mon_fmt.h"
@@ -464,32 +465,12 @@ extern "C" int shud_mon_time_flood(shud_mon_t m, int reps, double *ms_pass) {
     if (!m->have_flood) return shud_fail(SHUD_ERR_ARG, "shud_mon_time_flood: no flood monitor");
     HIP_TRY(hipSetDevice(m->device));
     if (mon_drain(m)) return mon_report(m);          // both banks idle: bank 0 is free to scribble on
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0.f;
-    auto pass = [&]() -> int {
+    return shud::time_passes(m->stream, reps, [&]() -> int {
         const int rc = flood_launch(m, 0);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(m->h_cnt[0], m->d_cnt[0], sizeof(int), hipMemcpyDeviceToHost, m->stream));
         return SHUD_OK;
-    };
-    auto timed = [&]() -> int {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        int rc = pass();                             // warm-up
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(e0, m->stream));
-        for (int k = 0; k < reps; k++)
-            if ((rc = pass())) return rc;
-        HIP_TRY(hipEventRecord(e1, m->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return SHUD_OK;
-    };
-    const int rc = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    *ms_pass = (double)ms / reps;
-    return rc;
+    }, ms_pass);
 }
 
 extern "C" int shud_mon_destroy(shud_mon_t m) {

@@ -4,23 +4,25 @@
 // Every kernel is one streaming pass over NY-long fp64 vectors in HBM, fusing the N_Vector operations that
 // CVODE issues back to back (cvode.c / sunlinsol_spgmr.c / nvector_serial.c) so each pass reads every operand
 // once.  Per element the arithmetic is exactly the serial N_Vector kernel's (same operations, same order, no
-// FMA contraction: -ffp-contract=off).  Reductions (dot products, WRMS norms, min) are deterministic: one entry
-// per thread on a full grid of kRedThreads-thread blocks writes per-block partials (waves in order), and a
-// one-block finalize kernel (kFinThreads threads, kFinAcc interleaved accumulators each) sums them in a fixed order
-// into a device scalar slot `ds[slot]` that later kernels read directly, and into its host-mapped twin
-// `hds[slot]` (with the RHS error word) that the host reads after a stream synchronize — no copy per fetch.
+// FMA contraction: -ffp-contract=off).  Reductions (dot products, WRMS norms, min) are deterministic: they go
+// through the project's one two-level reduction, shud_reduce.h — the single statement of the summation order,
+// shared with the water-balance diagnostics and pinned by tests/test_ode_kernels.py (CPU, against the oracle's
+// restatement) and tests/test_gpu_ode_kernels.py (every kernel here, bit for bit).  The one-block finalize kernel
+// leaves each result in a device scalar slot `ds[slot]` that later kernels read directly, and in its host-mapped
+// twin `hds[slot]` (with the RHS error word) that the host reads after a stream synchronize — no copy per fetch.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "shud_reduce.h"
+
 namespace shud {
 namespace ode {
 
+using namespace red;                // kRedThreads, kFinThreads, kFinAcc, ldn / stn, block_partial, ordered_total
+
 constexpr int kThreads = 256;       // element-wise passes
-constexpr int kRedThreads = 1024;   // reduction passes: one entry per thread, ceil(n / 1024) blocks
-constexpr int kFinThreads = 1024;   // finalize: thread t sums partials t + (kFinAcc*j + k)*kFinThreads into acc k
-constexpr int kFinAcc = 4;
 constexpr int kMaxAcc = 4;
 constexpr int kMaxL = 32;     // SPGMR Krylov dimension bound (maxl)
 constexpr int kQMax = 5;      // BDF

@@ -1,8 +1,8 @@
 // shud_ode_kernels.hip — device vector kernels of the integrator (see shud_ode_dev.h).
 //
 // Streaming passes over fp64 vectors of NY entries, one entry per thread on a full grid (element-wise passes in
-// 256-thread blocks, reductions in kRedThreads-thread blocks whose partials a one-block finalize sums in a fixed
-// order, so every reduction is deterministic), with non-temporal loads and stores.  Per element each kernel applies exactly the serial N_Vector operations CVODE
+// 256-thread blocks, reductions through shud_reduce.h: block_partial in kRedThreads-thread blocks, then a one-block
+// finalize, a fixed order), with non-temporal loads and stores.  Per element each kernel applies exactly the serial N_Vector operations CVODE
 // issues (nvector_serial.c: N_VLinearSum special cases, N_VScale, N_VProd/N_VDiv, N_VLinearCombination,
 // N_VScaleAddMulti) in the same order; the host controller (shud_ode.cpp) cites the CVODE routine each call
 // replaces.  The bound is HBM bandwidth: bytes per entry are listed at each kernel.
@@ -26,17 +26,8 @@ static int ew_blocks(int64_t n) {
     return (int)(b < 1 ? 1 : b);
 }
 
-// single-use streams: non-temporal loads and stores (global_load/store ... nt).  The vectors are NY-long (250 MB
-// at syn-10M), far beyond L2; nt loads+stores measured 7 % faster on the five-operand pass
-// (profiles/r03/ode/ode_red_bench.log)
-template <class T>
-__device__ __forceinline__ T ldn(const T *p) { return __builtin_nontemporal_load(p); }
-template <class T>
-__device__ __forceinline__ void stn(T *p, T v) { __builtin_nontemporal_store(v, p); }
-
-// One entry per thread: use(i, load(i)) for i = block * BS + thread when i < n (BS = blockDim.x).  Reductions run
-// on the full one-shot grid (ceil(n / kRedThreads) blocks) rather than a grid-stride loop: the grid-stride form
-// kept one load batch per wave in flight and ran at 4.7 TB/s against 5.7 TB/s one-shot (ode_red_bench).
+// One entry per thread: use(i, load(i)) for i = block * BS + thread when i < n (BS = blockDim.x); the vectors are
+// NY-long (250 MB at syn-10M), single-use streams through ldn / stn.
 template <class T, class Load, class Use>
 __device__ __forceinline__ void one(int64_t n, Load load, Use use) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,85 +45,17 @@ struct DN { double v[N]; };
 // element-wise kernel
 #define LAUNCH_EW(K, n, s, ...) K<1><<<ew_blocks(n), kThreads, 0, (s)>>>(n, __VA_ARGS__)
 
-__device__ inline double comb(double a, double b, bool mn) { return mn ? fmin(a, b) : a + b; }
-
-// the NW = threads/64 wave results of a block (sm[0..NW), one per wave) combined by wave 0: lane l < NW holds
-// sm[l], an xor butterfly over offsets NW/2 .. 1 (lanes >= NW never mix in), lane 0 keeps the result.  A fixed
-// tree order (oracle: waves_tree) in 4 shuffles — round 2's serial sum on thread 0 (16 dependent LDS reads per
-// accumulator) held every 1024-thread block's slot for ~1.5 us and slowed the light passes (k_ewt 105 -> 173 us)
-template <int NW>
-__device__ inline double waves_tree(const double *sm, bool mn, int lane) {
-    static_assert(NW <= 64 && (NW & (NW - 1)) == 0, "power-of-two wave count");
-    double x = lane < NW ? sm[lane] : (mn ? INFINITY : 0.0);
-#pragma unroll
-    for (int off = NW / 2; off >= 1; off >>= 1) x = comb(x, __shfl_xor(x, off, 64), mn);
-    return x;
-}
-
-// block partials: wave64 butterfly per wave, then the wave results by waves_tree (deterministic)
-template <int NACC>
-__device__ inline void block_partial(double (&v)[NACC], unsigned minmask, const Red &r) {
-    constexpr int NW = kRedThreads / 64;
-    __shared__ double sm[NACC][NW];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-        const bool mn = (minmask >> a) & 1u;
-        double x = v[a];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x = comb(x, __shfl_xor(x, off, 64), mn);
-        if (lane == 0) sm[a][wid] = x;
-    }
-    __syncthreads();
-    if (wid == 0) {
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) {
-            const bool mn = (minmask >> a) & 1u;
-            const double s = waves_tree<NW>(sm[a], mn, lane);
-            if (lane == 0) r.part[(int64_t)a * r.nblk + blockIdx.x] = s;
-        }
-    }
-}
-
-// the nblk partials of one reduction in a fixed order into the device slot ds[slot0 + a] (read by later kernels)
-// and its host-mapped twin hds[slot0 + a]; hds[S_COUNT] receives the RHS error word, so a host fetch is one stream
-// synchronize.  Order (restated by oracle/shud_oracle_ode.c device_order_sum): thread t keeps kFinAcc
-// accumulators, acc[k] over partials t + (kFinAcc*j + k)*kFinThreads for j = 0, 1, ... (the kFinAcc loads of one j
-// in flight together); x = (acc0 + acc1) + (acc2 + acc3); wave64 butterfly; the kFinThreads/64 wave results by
-// waves_tree.  (Finalizing in the producer's last-arriving block instead measured slower: tickets on one counter.)
+// the nblk partials of each of a reduction's nacc quantities by ordered_total (shud_reduce.h) into the device slot
+// ds[slot0 + a] (read by later kernels) and its host-mapped twin hds[slot0 + a]; hds[S_COUNT] receives the RHS error
+// word, so a host fetch is one stream synchronize
 __global__ void __launch_bounds__(kFinThreads) k_finalize(Red r, int nacc, unsigned minmask) {
-    constexpr int NW = kFinThreads / 64;
-    __shared__ double sm[NW];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ double sm[kFinThreads / 64];
     for (int a = 0; a < nacc; ++a) {
-        const bool mn = (minmask >> a) & 1u;
-        const double id = mn ? INFINITY : 0.0;
-        const double *pp = r.part + (int64_t)a * r.nblk;
-        double acc[kFinAcc];
-#pragma unroll
-        for (int k = 0; k < kFinAcc; ++k) acc[k] = id;
-        for (int b0 = threadIdx.x; b0 < r.nblk; b0 += kFinAcc * kFinThreads) {
-            double v[kFinAcc];
-#pragma unroll
-            for (int k = 0; k < kFinAcc; ++k) {
-                const int b = b0 + k * kFinThreads;
-                v[k] = b < r.nblk ? pp[b] : id;
-            }
-#pragma unroll
-            for (int k = 0; k < kFinAcc; ++k) acc[k] = comb(acc[k], v[k], mn);
+        const double s = ordered_total(r.part + (int64_t)a * r.nblk, r.nblk, (minmask >> a) & 1u, sm);
+        if (threadIdx.x == 0) {
+            r.ds[r.slot0 + a] = s;
+            r.hds[r.slot0 + a] = s;
         }
-        double x = comb(comb(acc[0], acc[1], mn), comb(acc[2], acc[3], mn), mn);
-        for (int off = 32; off >= 1; off >>= 1) x = comb(x, __shfl_xor(x, off, 64), mn);
-        if (lane == 0) sm[wid] = x;
-        __syncthreads();
-        if (wid == 0) {
-            const double s = waves_tree<NW>(sm, mn, lane);
-            if (lane == 0) {
-                r.ds[r.slot0 + a] = s;
-                r.hds[r.slot0 + a] = s;
-            }
-        }
-        __syncthreads();
     }
     if (threadIdx.x == 0 && r.err) {
         const uint32_t fl = *(const volatile uint32_t *)r.err;
@@ -165,7 +88,7 @@ __global__ void __launch_bounds__(kRedThreads) k_ewt(int64_t n, const double *__
         const double p = y * w;
         v[1] += p * p;
     });
-    block_partial<2>(v, 1u, r);
+    block_partial<2>(v, 1u, r.part, r.nblk);
 }
 void ewt_set(int64_t n, const double *zn0, double *ewt, double rtol, double atol, const Red &r, hipStream_t s) {
     LAUNCH_RED(k_ewt, r, s, n, zn0, ewt, rtol, atol);
@@ -339,7 +262,7 @@ __global__ void __launch_bounds__(kRedThreads) k_residual(int64_t n, const doubl
         const double p = d * o.d;
         v[0] += p * p;
     });
-    block_partial<1>(v, 0u, r);
+    block_partial<1>(v, 0u, r.part, r.nblk);
 }
 void residual(int64_t n, const double *zn1, const double *ycor, const double *ftemp, double rl1, double ngamma,
               const double *ewt, double *delta, const Red &r, hipStream_t s) {
@@ -359,7 +282,7 @@ __global__ void __launch_bounds__(kRedThreads) k_krylov_v0(int64_t n, const doub
         const double p = (x / w) * w;
         v[0] += p * p;
     });
-    block_partial<1>(v, 0u, r);
+    block_partial<1>(v, 0u, r.part, r.nblk);
 }
 void krylov_v0(int64_t n, const double *delta, const double *ewt, double c, double *V0, const Red &r, hipStream_t s) {
     LAUNCH_RED(k_krylov_v0, r, s, n, delta, ewt, c, V0);
@@ -401,7 +324,7 @@ __global__ void __launch_bounds__(kRedThreads) k_atimes(int64_t n, double *__res
         v[0] += x * x;
         v[1] += o.v[4] * x;
     });
-    block_partial<2>(v, 0u, r);
+    block_partial<2>(v, 0u, r.part, r.nblk);
 }
 void atimes(int64_t n, double *w, const double *fy, const double *V, const double *ewt, const double *V0,
             double ngamma, const double *ds, const Red &r, hipStream_t s) {
@@ -425,7 +348,7 @@ __global__ void __launch_bounds__(kRedThreads) k_mgs(int64_t n, double *__restri
         }
         v[0] += Vnext ? o.c * x : x * x;
     });
-    block_partial<1>(v, 0u, r);
+    block_partial<1>(v, 0u, r.part, r.nblk);
 }
 void mgs(int64_t n, double *w, const double *Vprev, const double *ds, int hslot, const double *Vnext, const Red &r,
          hipStream_t s) {
@@ -444,7 +367,7 @@ __global__ void __launch_bounds__(kRedThreads) k_normalize(int64_t n, double *__
         const double p = (x / e) * e;
         v[0] += p * p;
     });
-    block_partial<1>(v, 0u, r);
+    block_partial<1>(v, 0u, r.part, r.nblk);
 }
 void normalize(int64_t n, double *w, double c, const double *ewt, const Red &r, hipStream_t s) {
     LAUNCH_RED(k_normalize, r, s, n, w, c, ewt);
@@ -496,7 +419,7 @@ __global__ void __launch_bounds__(kRedThreads) k_newton_update(int64_t n, const 
         v[0] += p * p;
         v[1] += q * q;
     });
-    block_partial<2>(v, 0u, r);
+    block_partial<2>(v, 0u, r.part, r.nblk);
 }
 void newton_update(int64_t n, const double *V, int64_t vstride, int krydim, const Coefs &yg, const double *dsrc,
                    const double *ewt, double *ycor, bool ycor_zero, const Red &r, hipStream_t s) {
@@ -562,7 +485,7 @@ __global__ void __launch_bounds__(kRedThreads) k_complete_ewt(int64_t n, double 
         const double p = z0 * w;
         v[1] += p * p;
     });
-    block_partial<2>(v, 1u, r);
+    block_partial<2>(v, 1u, r.part, r.nblk);
 }
 void complete_step_ewt(int64_t n, double *zn, const double *acor, const Coefs &l, int q, int copy_to, int jst,
                        double rtol, double atol, double *ewt_next, const Red &r, hipStream_t s) {
@@ -592,7 +515,7 @@ __global__ void __launch_bounds__(kRedThreads) k_eta_norms(int64_t n, const doub
             v[1] += p * p;
         }
     });
-    block_partial<2>(v, 0u, r);
+    block_partial<2>(v, 0u, r.part, r.nblk);
 }
 void eta_norms(int64_t n, const double *zn_q, const double *zn_qmax, const double *acor, double ncquot,
                const double *ewt, int pend_q, double lq, const Red &r, hipStream_t s) {

@@ -19,13 +19,13 @@
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
-#include <cstring>
 #include <deque>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "shud_diag_host.h"
 #include "shud_handle.h"
 #include "shud_out.h"
 
@@ -233,27 +233,15 @@ extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) {
         HIP_TRY(hipMemcpy(p.d_sel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     // open_file: fixed 1024-byte header, StartTime, NumVar, icol (binary); the ASCII twin's preamble
-    char header[1024];
-    memset(header, 0, sizeof(header));
     const char *mode = s->solar_lonlat_mode ? s->solar_lonlat_mode : "";
-    snprintf(header, sizeof(header),
-             "# SHUD output\n"
-             "# Radiation input mode: %s\n"
-             "# Terrain radiation (TSR): %s\n"
-             "# Solar lon/lat mode: %s\n"
-             "# Solar lon/lat (deg): lon=%.6f, lat=%.6f\n",
-             s->radiation_input_mode == 1 ? "SWNET" : "SWDOWN", s->terrain_radiation ? "ON" : "OFF", mode,
-             s->solar_lon_deg, s->solar_lat_deg);
     if (s->binary) {
         const std::string fb = p.filename + ".dat";
         p.fb = fopen(fb.c_str(), "wb");
         if (!p.fb) return out_fail_io("shud_out_add", fb);
-        fwrite(header, sizeof(char), 1024, p.fb);
-        double tmp = (double)p.start_time;
-        fwrite(&tmp, sizeof(tmp), 1, p.fb);
-        tmp = (double)p.numvar;
-        fwrite(&tmp, sizeof(tmp), 1, p.fb);
-        fwrite(p.icol.data(), sizeof(double), p.icol.size(), p.fb);
+        // a failed write here is not reported; every row's write is checked (writer_loop)
+        (void)shud::write_dat_preamble(p.fb, nullptr, s->radiation_input_mode, s->terrain_radiation, mode,
+                                       s->solar_lon_deg, s->solar_lat_deg, (double)p.start_time, p.numvar,
+                                       p.icol.data());
     }
     if (s->ascii) {
         const std::string fa = p.filename + ".csv";

@@ -4,12 +4,13 @@
 // sample (:410-529) is one fused pass, one lane per element: it loads DY, Sy, area, the step inputs, ic_raw, the ET
 // components, the lateral totals and the six edge-major flux planes, forms the four per-element rates in the
 // reference's operation order and read-modify-writes the four accumulators (the previous-rate arrays exist only
-// in trapezoid mode).  The basin sums go through the integrator's two-level deterministic reduction
-// (shud_ode_kernels.hip block_partial / k_finalize): wave64 xor butterfly, the wave results combined by one wave
-// through LDS, one partial per workgroup and quantity (vector stores), and a one-block finalize that sums the
-// partials in index order and applies acc += rate*dt (or the trapezoid rule) to the seven basin accumulators on
-// the device.  No fp64 atomics: the results do not depend on scheduling.  A pass over the reaches gives the
-// outlet discharge (:197-230), the reach boundary-condition inflow and the river storage (:183-195) the same way.
+// in trapezoid mode).  The basin sums go through the project's one two-level deterministic reduction, shared with
+// the integrator: shud_reduce.h is the single statement of the summation order (block_partial per workgroup and
+// quantity, ordered_total per quantity in the one-block finalize), pinned for these sums bit for bit by
+// tests/test_gpu_wb.py::test_reduction_edges and tests/test_gpu_wb_quad.py::test_rates_reduction_edges against
+// tests/ode_kernels_py.py device_order_sum.  The finalize then applies acc += rate*dt (or the trapezoid rule) to
+// the seven basin accumulators on the device.  A pass over the reaches gives the outlet discharge (:197-230), the
+// reach boundary-condition inflow and the river storage (:183-195) the same way.
 // maybeWrite (:531-636) runs a residual pass at interval ends (four residual arrays, storage snapshots rolled,
 // accumulators zeroed, basin element storage reduced); only then do 4 NE + 9 doubles cross PCIe, synchronously
 // (once per output interval), and are written in the reference's byte layout (:90-150).
@@ -30,20 +31,19 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <string>
 #include <vector>
 
+#include "shud_diag_host.h"
 #include "shud_handle.h"
 #include "shud_out.h"
 #include "shud_physics.h"
+#include "shud_reduce.h"
 #include "shud_wb.h"
 
 namespace {
 
-constexpr int kBS = 1024;            // one entry per thread on a one-shot grid (ode::kRedThreads)
-constexpr int kFinThreads = 1024;    // finalize: thread t sums partials t + (kFinAcc*j + k)*kFinThreads into acc k
-constexpr int kFinAcc = 4;
+using namespace shud::red;           // every element / reach pass: one entry per thread on its kRedThreads grid
 // element-pass partials, reach-pass partials
 enum { EQ_P = 0, EQ_ET, EQ_QBC, EQ_QSS, EQ_NONCONS, EQ_QEDGE, EQ_N };
 enum { RQ_QOUT = 0, RQ_RBC, RQ_STOR, RQ_N };
@@ -58,34 +58,23 @@ constexpr int kFlagEdge = 16, kFlagSS = 19;
 // reach flags: bit 0 outlet (down < 0, not into a lake), bit 1 critical-depth outlet (down == -4)
 constexpr int kRivOutlet = 1, kRivCrit = 2;
 
-template <class T>
-__device__ __forceinline__ T ldn(const T *p) { return __builtin_nontemporal_load(p); }
-template <class T>
-__device__ __forceinline__ void stn(T *p, T v) { __builtin_nontemporal_store(v, p); }
-
-// block partials (sums): wave64 xor butterfly per wave, then the wave results by one wave through LDS, a fixed tree
-template <int NACC>
-__device__ inline void block_partial(double (&v)[NACC], double *__restrict__ part, int nblk) {
-    constexpr int NW = kBS / 64;
-    __shared__ double sm[NACC][NW];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+// the element's six basin terms (sample :472-489; the monitor's f(), MD_f.cpp:57-86,115-128), one place as in the
+// reference: qe[j] is QeleSurf + QeleSub of edge j, eqbc the element's boundary-condition flux (0.0 unless iBC < 0)
+__device__ __forceinline__ void basin_terms(double area, int fl, double prcp, double ic, double es, double eu,
+                                            double eg, double tu, double tg, const double (&qe)[3], double eqbc,
+                                            double (&v)[EQ_N]) {
+    v[EQ_P] = prcp * area;
+    v[EQ_ET] = (ic + es + eu + eg + tu + tg) * area;
+    v[EQ_QBC] = eqbc;
+    v[EQ_QSS] = 0.0;                                                   // QSS where iSS != 0: always 0.0
+    double nc = 0.0, qedge = 0.0;
 #pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-        double x = v[a];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-        if (lane == 0) sm[a][wid] = x;
+    for (int j = 0; j < 3; j++) {
+        if ((fl >> (kFlagEdge + j)) & 1) qedge += qe[j];
+        else nc += qe[j];
     }
-    __syncthreads();
-    if (wid == 0) {
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) {
-            double x = lane < NW ? sm[a][lane] : 0.0;
-#pragma unroll
-            for (int off = NW / 2; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-            if (lane == 0) part[(size_t)a * nblk + blockIdx.x] = x;
-        }
-    }
+    v[EQ_NONCONS] = nc;
+    v[EQ_QEDGE] = qedge;
 }
 
 struct SampleArgs {
@@ -101,8 +90,8 @@ struct SampleArgs {
 };
 
 // WaterBalanceDiag::sample, the per-element loop (:425-463) and the element half of the basin loop (:472-489)
-__global__ void __launch_bounds__(kBS) k_wb_sample(SampleArgs a) {
-    const int i = blockIdx.x * kBS + threadIdx.x;
+__global__ void __launch_bounds__(kRedThreads) k_wb_sample(SampleArgs a) {
+    const int i = blockIdx.x * kRedThreads + threadIdx.x;
     double v[EQ_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (i < a.n) {
         const size_t n = (size_t)a.n;
@@ -140,20 +129,9 @@ __global__ void __launch_bounds__(kBS) k_wb_sample(SampleArgs a) {
             }
             stn(a.acc[k] + i, acc);
         }
-        v[EQ_P] = prcp * area;
-        v[EQ_ET] = (ic + es + eu + eg + tu + tg) * area;
-        v[EQ_QBC] = QBC;                                               // 0.0 unless iBC < 0
-        v[EQ_QSS] = 0.0;                                               // QSS where iSS != 0: always 0.0
-        double nc = 0.0, qedge = 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            if ((fl >> (kFlagEdge + j)) & 1) qedge += qe[j];
-            else nc += qe[j];
-        }
-        v[EQ_NONCONS] = nc;
-        v[EQ_QEDGE] = qedge;
+        basin_terms(area, fl, prcp, ic, es, eu, eg, tu, tg, qe, QBC, v);
     }
-    block_partial<EQ_N>(v, a.part, a.nblk);
+    block_partial<EQ_N>(v, 0u, a.part, a.nblk);
 }
 
 struct RivArgs {
@@ -167,8 +145,8 @@ struct RivArgs {
 
 // basinOutletDischarge_m3min (:197-230), the reach half of the boundary-condition sum (:490-494) and
 // basinRiverStorage_m3 (:183-195), one lane per reach
-__global__ void __launch_bounds__(kBS) k_wb_river(RivArgs a) {
-    const int r = blockIdx.x * kBS + threadIdx.x;
+__global__ void __launch_bounds__(kRedThreads) k_wb_river(RivArgs a) {
+    const int r = blockIdx.x * kRedThreads + threadIdx.x;
     double v[RQ_N] = {0.0, 0.0, 0.0};
     if (r < a.nr) {
         const double stage = a.stage[r], len = a.len[r];
@@ -187,7 +165,7 @@ __global__ void __launch_bounds__(kBS) k_wb_river(RivArgs a) {
         if (bc < 0) v[RQ_RBC] = a.rqbc[-bc];
         v[RQ_STOR] = g.csarea * len;
     }
-    block_partial<RQ_N>(v, a.part, a.nblk);
+    block_partial<RQ_N>(v, 0u, a.part, a.nblk);
 }
 
 struct QuadArgs {
@@ -201,8 +179,8 @@ struct QuadArgs {
 
 // the element half of the basin rates f() forms for the monitor (MD_f.cpp:57-86,115-128): k_wb_sample's basin terms
 // without its per-element rates and accumulators.  Lanes past n carry 0.0 to the barrier in block_partial.
-__global__ void __launch_bounds__(kBS) k_wb_quad(QuadArgs a) {
-    const int i = blockIdx.x * kBS + threadIdx.x;
+__global__ void __launch_bounds__(kRedThreads) k_wb_quad(QuadArgs a) {
+    const int i = blockIdx.x * kRedThreads + threadIdx.x;
     double v[EQ_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (i < a.n) {
         const size_t n = (size_t)a.n;
@@ -214,20 +192,9 @@ __global__ void __launch_bounds__(kBS) k_wb_quad(QuadArgs a) {
 #pragma unroll
         for (int j = 0; j < 3; j++) qe[j] = ldn(a.qs + j * n + i) + ldn(a.qb + j * n + i);
         const int ibc = (int)(int16_t)(fl & 0xffff);
-        v[EQ_P] = prcp * area;
-        v[EQ_ET] = (ic + es + eu + eg + tu + tg) * area;
-        v[EQ_QBC] = ibc < 0 ? a.eqbc[-ibc] : 0.0;
-        v[EQ_QSS] = 0.0;                                               // QSS where iSS != 0: always 0.0
-        double nc = 0.0, qedge = 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            if ((fl >> (kFlagEdge + j)) & 1) qedge += qe[j];
-            else nc += qe[j];
-        }
-        v[EQ_NONCONS] = nc;
-        v[EQ_QEDGE] = qedge;
+        basin_terms(area, fl, prcp, ic, es, eu, eg, tu, tg, qe, ibc < 0 ? a.eqbc[-ibc] : 0.0, v);
     }
-    block_partial<EQ_N>(v, a.part, a.nblk);
+    block_partial<EQ_N>(v, 0u, a.part, a.nblk);
 }
 
 struct QuadRivArgs {
@@ -240,15 +207,15 @@ struct QuadRivArgs {
 
 // the reach half (MD_f.cpp:193-205): QrivDown as f() computed it where the reach is an outlet, qBC where BC < 0;
 // partial slots RQ_QOUT and RQ_RBC
-__global__ void __launch_bounds__(kBS) k_wb_quad_river(QuadRivArgs a) {
-    const int r = blockIdx.x * kBS + threadIdx.x;
+__global__ void __launch_bounds__(kRedThreads) k_wb_quad_river(QuadRivArgs a) {
+    const int r = blockIdx.x * kRedThreads + threadIdx.x;
     double v[2] = {0.0, 0.0};
     if (r < a.nr) {
         if (a.flags[r] & kRivOutlet) v[RQ_QOUT] = ldn(a.qdown + r);
         const int bc = a.bc[r];
         if (bc < 0) v[RQ_RBC] = a.rqbc[-bc];
     }
-    block_partial<2>(v, a.part, a.nblk);
+    block_partial<2>(v, 0u, a.part, a.nblk);
 }
 
 struct ResidArgs {
@@ -261,8 +228,8 @@ struct ResidArgs {
 };
 
 // maybeWrite's element loop (:553-569) and basinElementStorageFull_m3 (:168-181)
-__global__ void __launch_bounds__(kBS) k_wb_resid(ResidArgs a) {
-    const int i = blockIdx.x * kBS + threadIdx.x;
+__global__ void __launch_bounds__(kRedThreads) k_wb_resid(ResidArgs a) {
+    const int i = blockIdx.x * kRedThreads + threadIdx.x;
     double v[1] = {0.0};
     if (i < a.n) {
         const double sy = a.sy[i];
@@ -282,7 +249,7 @@ __global__ void __launch_bounds__(kBS) k_wb_resid(ResidArgs a) {
         a.sfull_prev[i] = sfull;
         v[0] = sfull * a.area[i];                                      // depth * area, depth == sfull bit for bit
     }
-    block_partial<1>(v, a.part, a.nblk);
+    block_partial<1>(v, 0u, a.part, a.nblk);
 }
 
 __global__ void __launch_bounds__(256) k_wb_ic(int n, const double *__restrict__ src, int stride, double *__restrict__ ic) {
@@ -301,43 +268,17 @@ struct FinArgs {
 };
 static_assert(RQ_QOUT == 0 && RQ_RBC == 1, "k_wb_quad_river fills the first two reach partial slots");
 
-// the partials of every quantity in a fixed order (k_finalize's: kFinAcc interleaved accumulators per thread,
-// (a0 + a1) + (a2 + a3), wave64 butterfly, the wave results by one wave), then the scalar update by thread 0.
-// One block strides over any number of partials: there is no single-pass limit.
+// the total of every quantity by ordered_total (shud_reduce.h), then the scalar update by thread 0
 __global__ void __launch_bounds__(kFinThreads) k_wb_finalize(FinArgs f) {
-    constexpr int NW = kFinThreads / 64;
-    __shared__ double sm[NW];
+    __shared__ double sm[kFinThreads / 64];
     __shared__ double tot[EQ_N + RQ_N];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int nq = f.ne_q + f.nr_q;
     for (int q = 0; q < nq; ++q) {
         const bool ele = q < f.ne_q;
         const int nblk = ele ? f.nblk_e : f.nblk_r;
         const double *pp = ele ? f.epart + (size_t)q * nblk : f.rpart + (size_t)(q - f.ne_q) * nblk;
-        double acc[kFinAcc];
-#pragma unroll
-        for (int k = 0; k < kFinAcc; ++k) acc[k] = 0.0;
-        for (int b0 = threadIdx.x; b0 < nblk; b0 += kFinAcc * kFinThreads) {
-            double v[kFinAcc];
-#pragma unroll
-            for (int k = 0; k < kFinAcc; ++k) {
-                const int b = b0 + k * kFinThreads;
-                v[k] = b < nblk ? pp[b] : 0.0;
-            }
-#pragma unroll
-            for (int k = 0; k < kFinAcc; ++k) acc[k] = acc[k] + v[k];
-        }
-        double x = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-        for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_xor(x, off, 64);
-        if (lane == 0) sm[wid] = x;
-        __syncthreads();
-        if (wid == 0) {
-            double y = lane < NW ? sm[lane] : 0.0;
-#pragma unroll
-            for (int off = NW / 2; off >= 1; off >>= 1) y = y + __shfl_xor(y, off, 64);
-            if (lane == 0) tot[q] = y;
-        }
-        __syncthreads();
+        const double y = ordered_total(pp, nblk, false, sm);
+        if (threadIdx.x == 0) tot[q] = y;
     }
     if (threadIdx.x != 0) return;
     double *s = f.s;
@@ -397,7 +338,7 @@ __global__ void __launch_bounds__(kFinThreads) k_wb_finalize(FinArgs f) {
     }
 }
 
-int blocks(int n) { return n > 0 ? (n + kBS - 1) / kBS : 0; }
+int blocks(int n) { return n > 0 ? (n + kRedThreads - 1) / kRedThreads : 0; }
 
 }  // namespace
 
@@ -458,26 +399,11 @@ static void wb_werr(shud_wb *w, const std::string &msg) {
 
 // writeDatHeader (:90-130)
 static void wb_header(shud_wb *w, int k, const char *label, int num_var, const ShudWbOptions *o) {
-    char header[1024];
-    memset(header, 0, sizeof(header));
-    snprintf(header, sizeof(header),
-             "# SHUD output\n"
-             "# Water-balance diagnostic: %s\n"
-             "# Radiation input mode: %s\n"
-             "# Terrain radiation (TSR): %s\n"
-             "# Solar lon/lat mode: %s\n"
-             "# Solar lon/lat (deg): lon=%.6f, lat=%.6f\n",
-             label, o->radiation_input_mode == 1 ? "SWNET" : "SWDOWN", o->terrain_radiation ? "ON" : "OFF",
-             o->solar_lonlat_mode ? o->solar_lonlat_mode : "", o->solar_lon_deg, o->solar_lat_deg);
-    FILE *fp = w->fp[k];
-    bool ok = fwrite(header, sizeof(char), 1024, fp) == 1024;
-    const double start_time = (double)o->forc_start_time, num_var_d = (double)num_var;
-    ok &= fwrite(&start_time, sizeof(double), 1, fp) == 1;
-    ok &= fwrite(&num_var_d, sizeof(double), 1, fp) == 1;
     std::vector<double> icol((size_t)num_var);
     for (int i = 0; i < num_var; i++) icol[(size_t)i] = (double)(i + 1);
-    if (num_var > 0) ok &= fwrite(icol.data(), sizeof(double), (size_t)num_var, fp) == (size_t)num_var;
-    if (!ok) wb_werr(w, "write error on " + w->fname[k]);
+    if (!shud::write_dat_preamble(w->fp[k], label, o->radiation_input_mode, o->terrain_radiation, o->solar_lonlat_mode,
+                                  o->solar_lon_deg, o->solar_lat_deg, (double)o->forc_start_time, num_var, icol.data()))
+        wb_werr(w, "write error on " + w->fname[k]);
 }
 
 // writeDatRecord (:132-150)
@@ -494,7 +420,7 @@ static int wb_launch_river(shud_wb *w) {
     if (w->NR <= 0) return 0;
     RivArgs a{w->NR, h->d_sum[3], w->d_rflags, w->d_rbc, w->d_rbw, w->d_rbs, w->d_rlen, w->d_rslope, w->d_rrough,
               h->dm.rqbc, w->d_rpart, w->nblk_r};
-    hipLaunchKernelGGL(k_wb_river, dim3(w->nblk_r), dim3(kBS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_wb_river, dim3(w->nblk_r), dim3(kRedThreads), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -512,7 +438,7 @@ static int wb_launch_storage(shud_wb *w, int mode) {
     a.s3_prev = w->d_s3; a.sfull_prev = w->d_sfull;
     a.init = mode == 2;
     a.part = w->d_epart; a.nblk = w->nblk_e;
-    hipLaunchKernelGGL(k_wb_resid, dim3(w->nblk_e), dim3(kBS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_wb_resid, dim3(w->nblk_e), dim3(kRedThreads), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     int rc = wb_launch_river(w);
     if (rc) return rc;
@@ -645,7 +571,7 @@ static int wb_sample_launch(shud_wb *w, double dt, const double *d_dy, bool has_
     for (int k = 0; k < 4; k++) { a.acc[k] = w->d_acc[k]; a.prev[k] = w->d_prev[k]; }
     a.dt = dt; a.trapz = w->trapz ? 1 : 0; a.has_prev = has_prev ? 1 : 0;
     a.part = w->d_epart; a.nblk = w->nblk_e;
-    hipLaunchKernelGGL(k_wb_sample, dim3(w->nblk_e), dim3(kBS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_wb_sample, dim3(w->nblk_e), dim3(kRedThreads), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     int rc = wb_launch_river(w);
     if (rc) return rc;
@@ -739,28 +665,13 @@ extern "C" int shud_wb_time_samples(shud_wb_t w, const double *d_dy, int reps, d
     if (!h->have_diag || (w->NR > 0 && !h->d_sum[3]))
         return shud_fail(SHUD_ERR_ARG, "shud_wb_time_samples: summary / diagnostics arrays missing");
     HIP_TRY(hipSetDevice(h->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0.f;
-    auto timed = [&]() -> int {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        int rc = wb_sample_launch(w, 1.0, d_dy, w->has_prev_rate);   // warm-up
-        if (rc) return rc;
-        w->has_prev_rate = true;
-        HIP_TRY(hipEventRecord(e0, h->stream));
-        for (int k = 0; k < reps; k++)
-            if ((rc = wb_sample_launch(w, 1.0, d_dy, true))) return rc;
-        HIP_TRY(hipEventRecord(e1, h->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return 0;
-    };
-    const int rc = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    const int rc = shud::time_passes(h->stream, reps, [&]() -> int {
+        const int r = wb_sample_launch(w, 1.0, d_dy, w->has_prev_rate);
+        if (!r) w->has_prev_rate = true;
+        return r;
+    }, ms_sample);
     w->last_t += 1.0 * (reps + 1);
     w->sampled = true;
-    *ms_sample = (double)ms / reps;
     return rc;
 }
 
@@ -788,11 +699,11 @@ static int wb_quad_launch(shud_wb *w, double dt, bool has_prev) {
     const DevDiag &g = h->dd;
     QuadArgs a{w->NE, w->d_area, w->d_flags, h->dm.prcp, w->d_ic, g.q_es, g.q_eu, g.q_eg, g.q_tu, g.q_tg,
                g.qele_surf, g.qele_sub, h->dm.eqbc, w->d_epart, w->nblk_e};
-    hipLaunchKernelGGL(k_wb_quad, dim3(w->nblk_e), dim3(kBS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_wb_quad, dim3(w->nblk_e), dim3(kRedThreads), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     if (w->NR > 0) {
         QuadRivArgs r{w->NR, w->d_rflags, w->d_rbc, g.qriv_down, h->dm.rqbc, w->d_rpart, w->nblk_r};
-        hipLaunchKernelGGL(k_wb_quad_river, dim3(w->nblk_r), dim3(kBS), 0, h->stream, r);
+        hipLaunchKernelGGL(k_wb_quad_river, dim3(w->nblk_r), dim3(kRedThreads), 0, h->stream, r);
         HIP_TRY(hipGetLastError());
     }
     FinArgs f{w->d_epart, w->d_rpart, EQ_N, w->nblk_e, 2, w->nblk_r, 3, w->open ? 1 : 0, 1, has_prev ? 1 : 0, dt,
@@ -851,27 +762,12 @@ extern "C" int shud_wb_time_quad(shud_wb_t w, int reps, double *ms_pass) {
     shud_rhs *h = w->h;
     if (!wb_have_fluxes(h)) return shud_fail(SHUD_ERR_ARG, "shud_wb_time_quad: diagnostics arrays missing");
     HIP_TRY(hipSetDevice(h->device));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0.f;
-    auto timed = [&]() -> int {
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        int rc = wb_quad_launch(w, 1.0, w->quad_has_prev);          // warm-up
-        if (rc) return rc;
-        w->quad_has_prev = true;
-        HIP_TRY(hipEventRecord(e0, h->stream));
-        for (int k = 0; k < reps; k++)
-            if ((rc = wb_quad_launch(w, 1.0, true))) return rc;
-        HIP_TRY(hipEventRecord(e1, h->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return 0;
-    };
-    const int rc = timed();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    const int rc = shud::time_passes(h->stream, reps, [&]() -> int {
+        const int r = wb_quad_launch(w, 1.0, w->quad_has_prev);
+        if (!r) w->quad_has_prev = true;
+        return r;
+    }, ms_pass);
     w->quad_last_t += 1.0 * (reps + 1);
-    *ms_pass = (double)ms / reps;
     return rc;
 }
 

@@ -3,9 +3,11 @@
 Every kernel there uses only IEEE-exact operations without contraction (+, -, *, /, sqrt, fmin, fabs), so the same
 expression in the same order in numpy is a bit-exact reference: no tolerance anywhere.
 
-Reductions: device_order_sum / device_order_min restate the device order from the kernel source (block_partial,
-waves_tree, k_finalize and the comment above it), not from the C oracle; tests/test_ode_kernels.py pins them
-against the oracle's own restatement and against math.fsum.
+Reductions: device_order_sum / device_order_min restate the device order from its one statement in the source
+(shud-up_amd/csrc/shud_reduce.h: block_partial, waves_tree, ordered_total and the comment at its head), not from the
+C oracle; tests/test_ode_kernels.py pins them against the oracle's own restatement and against math.fsum.  The
+water-balance kernels (shud_wb.hip) sum through the same header, so tests/test_gpu_wb.py and
+tests/test_gpu_wb_quad.py hold their basin sums to device_order_sum as well.
 
 Launchers: one function per launcher of shud_ode_dev.h.  Each returns (outputs, accs): outputs maps a vector name
 to its new value (zn is the whole (columns, n) slab), accs lists (terms, is_min) per accumulator in slot order —
@@ -43,19 +45,20 @@ def _tree(x, op):
     return x[..., 0]
 
 
-def block_partials(term, ident, op):
+def block_partials(term, ident, op, accumulated=True):
     """block_partial: thread i holds ident op term[i] (lanes past n: ident); wave64 butterfly (offsets 32 .. 1),
-    then the 16 wave results by waves_tree (offsets 8 .. 1).  One partial per block of 1024."""
+    then the 16 wave results by waves_tree (offsets 8 .. 1).  One partial per block of 1024.
+    accumulated=False: the lane holds term[i] itself, as in the water-balance kernels (v = term, not v += term)."""
     term = np.asarray(term, dtype=np.float64)
     nb = grid_blocks(term.size)
     lanes = np.full(nb * RED_THREADS, ident)
-    lanes[:term.size] = op(ident, term)
+    lanes[:term.size] = op(ident, term) if accumulated else term
     waves = _tree(lanes.reshape(nb, RED_THREADS // 64, 64), op)
     return _tree(waves, op)
 
 
 def finalize(part, ident, op, fin_acc=FIN_ACC):
-    """k_finalize: lane t, acc[k] op= part[t + (fin_acc*j + k)*1024] for j = 0, 1, ... (identity past nblk);
+    """ordered_total: lane t, acc[k] op= part[t + (fin_acc*j + k)*1024] for j = 0, 1, ... (identity past nblk);
     (acc0 op acc1) op (acc2 op acc3); wave butterfly; waves_tree.  fin_acc = 1 is the single-accumulator tree the
     discriminating-power test compares with (not a device order)."""
     span = fin_acc * FIN_THREADS

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import cases
+import ode_kernels_py
 import wb_py
 from conftest import ATOL, PKG_DIR, RTOL
 from shud_rhs import abi, et, host, partition, shudio, synth, workload
@@ -161,6 +162,14 @@ def _check_bound(name, got, terms, must_be_live=False):
     assert abs(got - ref) <= bound, (name, got, ref, bound)
 
 
+def _check_order(name, got, terms):
+    """the same bits as the one reduction order of the device (csrc/shud_reduce.h, shared with the integrator) as
+    tests/ode_kernels_py.py restates it; terms: one per element in index order, fp64 numpy, left to right"""
+    want = ode_kernels_py.device_order_sum(np.asarray(terms, dtype=np.float64))
+    print(f"{name}: gpu={got!r} device_order_sum={want!r}")
+    assert np.float64(got).view(np.uint64) == np.float64(want).view(np.uint64), (name, got, want)
+
+
 @pytest.mark.parametrize("ne", [1, 63, 64, 65, 255, 256, 257, 2000, 1_060_000, 4_250_000])
 def test_reduction_edges(ne):
     """Sizes around the wave (64) and quarter-workgroup edges, and NE = 2000 (two 1024-lane workgroups, +-BC
@@ -183,6 +192,7 @@ def test_reduction_edges(ne):
     st = rig.state()
     g0 = wbs[0].read(arrays=False)
     _check_bound("storage_ele", g0["storage"][0], sfull_of(m, st) * m.ele["area"], must_be_live=True)
+    _check_order("storage_ele", g0["storage"][0], sfull_of(m, st) * m.ele["area"])
     _check_bound("storage_riv", g0["storage"][1], wb_py.river_storage_terms(m, st[3]), must_be_live=m.num_riv > 0)
     rig.advance(12.5, workload.random_state(m, seed=9))
     dy = np.random.default_rng(ne).normal(0.0, 1e-4, m.num_y)
@@ -199,8 +209,11 @@ def test_reduction_edges(ne):
     rate = g["basin_rate"]
     assert np.array_equal(g["basin_acc"], rate * 12.5)
     _check_bound("P", rate[abi.SHUD_WB_P], m.step["prcp"] * m.ele["area"], must_be_live=True)
+    _check_order("P", rate[abi.SHUD_WB_P], m.step["prcp"] * m.ele["area"])
     _check_bound("ET", rate[abi.SHUD_WB_ET],
                  (ic + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * m.ele["area"], must_be_live=True)
+    _check_order("ET", rate[abi.SHUD_WB_ET],
+                 (ic + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * m.ele["area"])
     _check_bound("Qout", rate[abi.SHUD_WB_QOUT], wb_py.outlet_terms(m, st[3])[wb_py.outlet_list(m)],
                  must_be_live=ne >= 2000)
     _check_bound("Qedge", rate[abi.SHUD_WB_QEDGE], qe[nb < 0], must_be_live=True)
@@ -219,6 +232,7 @@ def test_reduction_edges(ne):
     for key in ga:
         assert np.array_equal(np.asarray(ga[key]), np.asarray(gb[key]), equal_nan=True), key
     _check_bound("storage_ele@write", ga["storage"][0], sfull_of(m, st) * m.ele["area"], must_be_live=True)
+    _check_order("storage_ele@write", ga["storage"][0], sfull_of(m, st) * m.ele["area"])
     for w in wbs:
         w.close()
     rig.close()

@@ -63,8 +63,11 @@ def test_rates_reduction_edges(ne):
     outs = wb_py.outlet_list(m)
     big = ne >= 2000
     tw._check_bound("P", rate[abi.SHUD_WB_P], m.step["prcp"] * m.ele["area"], must_be_live=True)
+    tw._check_order("P", rate[abi.SHUD_WB_P], m.step["prcp"] * m.ele["area"])
     tw._check_bound("ET", rate[abi.SHUD_WB_ET],
                     (ic + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * m.ele["area"], must_be_live=True)
+    tw._check_order("ET", rate[abi.SHUD_WB_ET],
+                    (ic + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * m.ele["area"])
     tw._check_bound("Qout", rate[abi.SHUD_WB_QOUT], d["qriv_down"][outs], must_be_live=big)
     tw._check_bound("Qedge", rate[abi.SHUD_WB_QEDGE], qe[nb < 0], must_be_live=True)
     tw._check_bound("Qbc", rate[abi.SHUD_WB_QBC], np.concatenate([wb_py.ele_qbc(m)[np.asarray(m.ibc) < 0],

@@ -99,6 +99,20 @@ def test_integer_family_closed_form(n):
     assert sum(K.integer_counts(n)) == n
 
 
+def test_sum_unchanged_by_unaccumulated_lanes():
+    """The water-balance kernels go through the same reduction but hand block_partial the term itself where the
+    integrator's hand it 0.0 + term.  The two differ only for a term of -0.0 (0.0 + -0.0 = +0.0), and a -0.0 survives
+    the block's tree only if every lane of the 1024-block holds one: so the partials, and with them the total, are
+    the same bits whenever not every term of a block is -0.0.  Condition on the inputs here: strictly positive.
+    (A per-block property: the small sizes, up to 17 blocks with a one-lane tail, cover it.)"""
+    for n in K.SMALL_SIZES:
+        term = np.abs(_signed_term(n)) + 2.0 ** -1000
+        assert (term > 0.0).all()
+        part = K.block_partials(term, 0.0, np.add, accumulated=False)
+        assert np.array_equal(part.view(np.uint64), K.block_partials(term, 0.0, np.add).view(np.uint64)), n
+        assert _bits(K.finalize(part, 0.0, np.add)) == _bits(K.device_order_sum(term)) == _bits(_oracle_sum(term)), n
+
+
 def test_device_order_min():
     """fmin tree: identity +inf, a NaN operand is dropped, position of the minimum does not matter"""
     rng = np.random.default_rng(3)
