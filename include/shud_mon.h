@@ -60,6 +60,10 @@ typedef struct {
 } ShudIcSpec;
 /* PrintInit's sources and schedule: once per monitor set */
 int shud_mon_add_ic(shud_mon_t m, const ShudIcSpec *s);
+/* The element arrays of the snapshot are in an internal numbering (include/shud_order.h): perm[k] (host, n_ele) is
+ * the caller's index of source element k, and the file lists the elements in the caller's order.  After
+ * shud_mon_add_ic; applies to every later snapshot. */
+int shud_mon_set_ic_order(shud_mon_t m, const int32_t *perm);
 /* PrintInit(Init_update, t): a snapshot is due iff ((unsigned long)(long)t) % update_ic_step == 0.  Returns 1 when
  * a snapshot of the arrays' current contents (stream-ordered) was queued, 0 when not due, < 0 on error.  Every
  * snapshot replaces the previous file. */

@@ -103,6 +103,10 @@ typedef struct {
 int shud_out_create(int device, void *stream, shud_out_t *out);
 /* Print_Ctrl::Init[IJ] + open_file: creates/truncates the files and writes their headers */
 int shud_out_add(shud_out_t o, const ShudPrintSpec *spec);
+/* shud_out_add over a source in another numbering (include/shud_order.h): column c of the file reads
+ * d_src[col_src[c]], col_src host [n_all] with values in [0, n_all); flag_io and the header's column numbers are
+ * still indexed by the caller's column c.  A create-time change: the export kernel already reads index lists. */
+int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *spec, const int32_t *col_src);
 /* Control_Data::ExportResults(t): every control adds its source into its buffer; controls whose interval
  * ends at t (floor(t + 0.001) % Interval == 0) write the interval mean and reset.  Sources must hold the
  * values to export (shud_rhs_summary / shud_rhs_refresh_diagnostics first), stream-ordered.  The rows of a

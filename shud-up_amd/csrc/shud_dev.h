@@ -15,6 +15,7 @@ struct DevErr {                      // per-handle device error word (ShudErr on
     int32_t first_index[8];          // slot = log2(bit); INT32_MAX = none
     unsigned long long n_warn;       // host side: sum of the slots
     unsigned long long *warn;        // [kWarnSlots * kWarnStride] device counters
+    const int *map;                  // ordered handle: internal element -> caller's index (first_index is the caller's); else null
 };
 
 struct DevMesh {

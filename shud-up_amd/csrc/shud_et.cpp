@@ -15,6 +15,7 @@
 #include "shud_out.h"
 #include "shud_et_dev.h"
 #include "shud_handle.h"
+#include "shud_order.h"
 
 struct EtState {
     DevEt e{};
@@ -50,6 +51,28 @@ extern "C" int shud_et_attach(shud_rhs_t h, const ShudEtMeshSoA *m, const ShudEt
         return shud_fail(SHUD_ERR_ARG, "terrain_radiation needs element normals");
     if (p->cryosphere && (p->ft_surf_day < 0 || p->ft_sub_day < 0))
         return shud_fail(SHUD_ERR_ARG, "bad cryosphere accumulator length");
+    // ordered handle (include/shud_order.h): the caller's [NE] arrays gathered into the internal numbering
+    ShudEtMeshSoA g;
+    std::vector<std::vector<int32_t>> gi;
+    std::vector<std::vector<double>> gd;
+    if (h->ordered) {
+        g = *m;
+        const int32_t **fi[] = {&g.iforc, &g.ilc, &g.imf, &g.ilake};
+        const double **fd[] = {&g.z_surf, &g.albedo, &g.fix_pressure, &g.wind_h, &g.veg_frac, &g.nx, &g.ny, &g.nz};
+        for (auto pp : fi) {
+            if (!*pp) continue;
+            gi.emplace_back((size_t)NE);
+            shud_order_gather_host(h->perm.data(), NE, sizeof(int32_t), 1, *pp, gi.back().data());
+            *pp = gi.back().data();
+        }
+        for (auto pp : fd) {
+            if (!*pp) continue;
+            gd.emplace_back((size_t)NE);
+            shud_order_gather_host(h->perm.data(), NE, sizeof(double), 1, *pp, gd.back().data());
+            *pp = gd.back().data();
+        }
+        m = &g;
+    }
     int mx[3] = {-1, -1, -1};
     for (int i = 0; i < NE; i++) {
         if (m->iforc[i] < 0 || m->ilc[i] < 1 || m->imf[i] < 1)
@@ -107,6 +130,16 @@ extern "C" int shud_et_set_state(shud_rhs_t h, const double *y_is, const double 
     if (!h || !h->et) return shud_fail(SHUD_ERR_ARG, "no ET prelude attached");
     HIP_TRY(hipSetDevice(h->device));
     const size_t nb = (size_t)h->NE * sizeof(double);
+    std::vector<double> g[2];
+    if (h->ordered) {                     // host pointers are in the caller's numbering
+        const double **src[2] = {&y_is, &y_snow};
+        for (int k = 0; k < 2; k++) {
+            if (!*src[k]) continue;
+            g[k].resize((size_t)h->NE);
+            shud_order_gather_host(h->perm.data(), h->NE, sizeof(double), 1, *src[k], g[k].data());
+            *src[k] = g[k].data();
+        }
+    }
     if (y_is) HIP_TRY(hipMemcpy(h->et->e.y_is, y_is, nb, hipMemcpyHostToDevice));
     if (y_snow) HIP_TRY(hipMemcpy(h->et->e.y_snow, y_snow, nb, hipMemcpyHostToDevice));
     return SHUD_OK;
@@ -229,8 +262,16 @@ extern "C" int shud_et_get(shud_rhs_t h, ShudEtOut *o) {
         {o->qPotTran, e.q_ptr}, {o->qEleETP, e.q_etp}, {o->qEleNetPrep, e.q_netp}, {o->qEleE_IC, eic},
         {o->yEleIS, e.y_is}, {o->yEleSnow, e.y_snow}, {o->fu_surf, e.fu_surf}, {o->fu_sub, e.fu_sub},
         {o->rn_factor, e.rn_factor}};
-    for (auto &x : m)
-        if (x.dst) HIP_TRY(hipMemcpy(x.dst, x.src, nb, hipMemcpyDeviceToHost));
+    std::vector<double> tmp(h->ordered ? (size_t)h->NE : 0);
+    for (auto &x : m) {
+        if (!x.dst) continue;
+        if (!h->ordered) {
+            HIP_TRY(hipMemcpy(x.dst, x.src, nb, hipMemcpyDeviceToHost));
+            continue;
+        }
+        HIP_TRY(hipMemcpy(tmp.data(), x.src, nb, hipMemcpyDeviceToHost));      // back to the caller's numbering
+        shud_order_gather_host(h->inv.data(), h->NE, sizeof(double), 1, tmp.data(), x.dst);
+    }
     return SHUD_OK;
 }
 

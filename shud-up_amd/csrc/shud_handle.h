@@ -73,6 +73,13 @@ struct shud_rhs {
     double *d_tab[4] = {nullptr, nullptr, nullptr, nullptr};
     int tab_len[4] = {0, 0, 0, 0};
 
+    // element ordering (include/shud_order.h): ordered = the device side runs in the internal numbering perm[]
+    int order_kind = 0;                  // SHUD_ORDER_*
+    bool ordered = false;                // perm is not the identity: host pointers are carried across
+    std::vector<int> perm, inv;          // perm[internal] = caller, inv[caller] = internal
+    int *d_perm = nullptr, *d_inv = nullptr;
+    double *d_stage = nullptr;           // max(ny, 3 NE) doubles: the caller-numbered side of a host-pointer copy
+
     EtState *et = nullptr;               // ET-step prelude (shud_et_attach), owned
     // output path (shud_out.h): Model_Data::summary arrays and the derived ET sums, allocated on first use
     double *d_sum[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // yEleSurf/Unsat/GW, yRivStg, yLakeStg
@@ -153,4 +160,7 @@ int shud_read_err(shud_rhs *h);          // h_err = the device error word (warni
 int shud_diag_replay(shud_rhs *h);       // shud_rhs.cpp: last eval again with diagnostic stores (device only)
 int shud_ensure_diag(shud_rhs *h);       // shud_rhs.cpp: allocate the DevDiag arrays (zeros) once
 void shud_et_free(shud_rhs *h);          // shud_et.cpp
+namespace shud {                         // shud_perm.hip: dst[p*n + i] = src[p*n + idx[i]], then ntail doubles copied
+void launch_perm_kernel(const int *idx, int n, int planes, const double *src, double *dst, int ntail, hipStream_t s);
+}
 const double *shud_et_array(shud_rhs *h, int which);   // shud_et.cpp: SHUD_ARR_Y_ELE_IS.. (NULL if not attached)

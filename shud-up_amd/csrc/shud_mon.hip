@@ -114,6 +114,7 @@ struct IcSrc {
     const double *col[5];                // yEleIS, yEleSnow, yEleSurf, yEleUnsat, yEleGW
     const double *riv, *lake;
     int ne, nr, nl;
+    const int *inv;                      // shud_mon_set_ic_order: file row c reads source element inv[c]; nullptr = c
 };
 
 // pack = [ne][5] row-major | riv[nr] | lake[nl]
@@ -123,8 +124,10 @@ __global__ void __launch_bounds__(kB) k_ic_pack(IcSrc s, double *__restrict__ pa
     const int i = base + threadIdx.x;
     if (base < s.ne) {
         const int cnt = min(kB, s.ne - base);
-        if (threadIdx.x < cnt)
-            for (int k = 0; k < 5; k++) tile[threadIdx.x * 5 + k] = s.col[k][i];
+        if (threadIdx.x < cnt) {
+            const int e = s.inv ? s.inv[i] : i;
+            for (int k = 0; k < 5; k++) tile[threadIdx.x * 5 + k] = s.col[k][e];
+        }
         __syncthreads();
         double *out = pack + (size_t)base * 5;
         for (int j = threadIdx.x; j < cnt * 5; j += kB) out[j] = tile[j];
@@ -168,6 +171,7 @@ struct shud_mon {
     std::string ipath;
     int step = 0;
     IcSrc src{};
+    int *d_inv = nullptr;                // IcSrc::inv
     size_t npack = 0;
     double *d_pack = nullptr, *h_pack[2] = {nullptr, nullptr};
     hipEvent_t ev_ik = nullptr, ev_ic[2] = {nullptr, nullptr};
@@ -404,12 +408,31 @@ extern "C" int shud_mon_add_ic(shud_mon_t m, const ShudIcSpec *s) {
     m->ipath = s->path_update;
     m->step = s->update_ic_step;
     m->src = IcSrc{{s->d_is, s->d_snow, s->d_surf, s->d_unsat, s->d_gw}, s->d_riv, s->d_lake, s->n_ele, s->n_riv,
-                   s->n_lake};
+                   s->n_lake, nullptr};
     m->npack = (size_t)s->n_ele * 5 + s->n_riv + s->n_lake;
     const size_t nb = std::max<size_t>(m->npack, 1) * sizeof(double);
     HIP_TRY(hipMalloc(&m->d_pack, nb));
     for (int b = 0; b < 2; b++) HIP_TRY(hipHostMalloc(&m->h_pack[b], nb, hipHostMallocDefault));
     m->have_ic = true;
+    return SHUD_OK;
+}
+
+extern "C" int shud_mon_set_ic_order(shud_mon_t m, const int32_t *perm) {
+    if (!m || !perm) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (!m->have_ic) return shud_fail(SHUD_ERR_ARG, "shud_mon_set_ic_order: no snapshot monitor (shud_mon_add_ic)");
+    const int ne = m->src.ne;
+    std::vector<int> inv((size_t)std::max(ne, 1), -1);
+    for (int k = 0; k < ne; k++) {
+        if (perm[k] < 0 || perm[k] >= ne || inv[perm[k]] >= 0)
+            return shud_fail(SHUD_ERR_ARG, "shud_mon_set_ic_order: not a permutation at entry %d", k);
+        inv[perm[k]] = k;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->d_inv) HIP_TRY(hipMalloc(&m->d_inv, inv.size() * sizeof(int)));
+    // stream-ordered after the pack kernels already enqueued, before the next one
+    HIP_TRY(hipMemcpyAsync(m->d_inv, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    m->src.inv = m->d_inv;
     return SHUD_OK;
 }
 
@@ -493,6 +516,7 @@ extern "C" int shud_mon_destroy(shud_mon_t m) {
     if (m->d_depth) (void)hipFree(m->d_depth);
     if (m->d_blk) (void)hipFree(m->d_blk);
     if (m->d_pack) (void)hipFree(m->d_pack);
+    if (m->d_inv) (void)hipFree(m->d_inv);
     for (int b = 0; b < 2; b++) {
         if (m->d_rec[b]) (void)hipFree(m->d_rec[b]);
         if (m->d_cnt[b]) (void)hipFree(m->d_cnt[b]);

@@ -879,10 +879,28 @@ static int ode_alloc(shud_ode *o, double t0, const double *y0, int where, const 
     HIP_TRY(hipHostGetDevicePointer((void **)&o->red.hds, o->h_ds, 0));
     o->red.ds = o->d_ds;
     o->red.err = o->rh ? &o->rh->d_err->flags : nullptr;
-    HIP_TRY(hipMemcpyAsync(o->zn, y0, n * sizeof(double),
+    // an ordered handle (include/shud_order.h): a host y0 is in the caller's numbering, the vectors are internal
+    const bool carry = where == SHUD_WHERE_HOST && o->rh && o->rh->ordered;
+    HIP_TRY(hipMemcpyAsync(carry ? o->rh->d_stage : o->zn, y0, n * sizeof(double),
                            where == SHUD_WHERE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o->s));
+    if (carry) {
+        launch_perm_kernel(o->rh->d_perm, o->rh->NE, 3, o->rh->d_stage, o->zn, o->rh->n_own_riv + o->rh->NL, o->s);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(o->s));
     return SHUD_OK;
+}
+
+// tempv -> a host pointer; through the stage and into the caller's numbering on an ordered handle
+static hipError_t ode_to_host(shud_ode *o, double *dst) {
+    const double *src = o->tempv;
+    if (o->rh && o->rh->ordered) {
+        launch_perm_kernel(o->rh->d_inv, o->rh->NE, 3, o->tempv, o->rh->d_stage, o->rh->n_own_riv + o->rh->NL, o->s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = o->rh->d_stage;
+    }
+    return hipMemcpyAsync(dst, src, o->n * sizeof(double), hipMemcpyDeviceToHost, o->s);
 }
 
 static void ode_free(shud_ode *o) {
@@ -943,8 +961,7 @@ extern "C" int shud_ode_solve(shud_ode_t o, double tout, double *y_out, int wher
     double *dst = (y_out && where == SHUD_WHERE_HOST) ? o->tempv : y_out;   // tempv is free between calls
     int rc = o->solve(tout, dst, tret, itask);
     if (y_out && where == SHUD_WHERE_HOST && rc >= 0) {
-        if (hipMemcpyAsync(y_out, o->tempv, o->n * sizeof(double), hipMemcpyDeviceToHost, o->s) != hipSuccess)
-            return SHUD_ODE_DEVICE_ERR;
+        if (ode_to_host(o, y_out) != hipSuccess) return SHUD_ODE_DEVICE_ERR;
     }
     if (hipStreamSynchronize(o->s) != hipSuccess) return SHUD_ODE_DEVICE_ERR;
     return rc;
@@ -955,9 +972,7 @@ extern "C" int shud_ode_get_dky(shud_ode_t o, double t, int k, double *dky, int 
     double *dst = where == SHUD_WHERE_HOST ? o->tempv : dky;
     int rc = o->get_dky(t, k, dst);
     if (rc != SHUD_ODE_SUCCESS) return rc;
-    if (where == SHUD_WHERE_HOST &&
-        hipMemcpyAsync(dky, o->tempv, o->n * sizeof(double), hipMemcpyDeviceToHost, o->s) != hipSuccess)
-        return SHUD_ODE_DEVICE_ERR;
+    if (where == SHUD_WHERE_HOST && ode_to_host(o, dky) != hipSuccess) return SHUD_ODE_DEVICE_ERR;
     if (hipStreamSynchronize(o->s) != hipSuccess) return SHUD_ODE_DEVICE_ERR;
     return SHUD_ODE_SUCCESS;
 }

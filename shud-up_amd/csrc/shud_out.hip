@@ -202,8 +202,13 @@ extern "C" int shud_out_create(int device, void *stream, shud_out_t *out) {
 }
 
 // Print_Ctrl::Init / InitIJ (Model_Control.cpp:759-858) + open_file (:683-758)
-extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) {
+// col_src (NULL: identity): caller column c reads d_src[col_src[c]]; flag_io and the header's icol stay by caller column
+static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src) {
     if (!o || !s || !s->basename || !s->d_src) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (col_src)
+        for (int i = 0; i < s->n_all; i++)
+            if (col_src[i] < 0 || col_src[i] >= s->n_all)
+                return shud_fail(SHUD_ERR_ARG, "Print_Ctrl %s: col_src[%d] = %d outside the source", s->basename, i, col_src[i]);
     if (s->interval == 0) return shud_fail(SHUD_ERR_ARG, "Print_Ctrl %s: interval 0 (reference: myexit(ERRCONSIS))",
                                            s->basename);
     if (s->n_all < 0 || s->interval < 0) return shud_fail(SHUD_ERR_ARG, "bad n_all / interval");
@@ -218,7 +223,7 @@ extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) {
     std::vector<int> sel;
     for (int i = 0; i < s->n_all; i++) {
         if (s->flag_io && !s->flag_io[i]) continue;
-        sel.push_back(i);
+        sel.push_back(col_src ? col_src[i] : i);
         p.icol.push_back((double)(i + 1));                       // icol[k] = (double)(i + 1)
     }
     p.numvar = (int)sel.size();
@@ -228,7 +233,7 @@ extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) {
     HIP_TRY(hipMalloc(&p.d_snap, nb * sizeof(double)));
     HIP_TRY(hipMemsetAsync(p.d_buf, 0, nb * sizeof(double), o->stream));   // buffer[k] = 0.0
     for (int b = 0; b < 2; b++) HIP_TRY(hipHostMalloc(&p.h_buf[b], nb * sizeof(double), hipHostMallocDefault));
-    if (s->flag_io && p.numvar < s->n_all) {
+    if (col_src || (s->flag_io && p.numvar < s->n_all)) {
         HIP_TRY(hipMalloc(&p.d_sel, nb * sizeof(int)));
         HIP_TRY(hipMemcpy(p.d_sel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -270,6 +275,12 @@ extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) {
                            o->stream));
     HIP_TRY(hipStreamSynchronize(o->stream));
     return SHUD_OK;
+}
+
+extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) { return out_add(o, s, nullptr); }
+extern "C" int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src) {
+    if (!col_src) return shud_fail(SHUD_ERR_ARG, "shud_out_add_mapped: null col_src");
+    return out_add(o, s, col_src);
 }
 
 // Control_Data::ExportResults (Model_Control.cpp:123-127) -> Print_Ctrl::PrintData (:926-960) for every control

@@ -268,6 +268,19 @@ __device__ __forceinline__ double da_to_dy(double dA, double w_top, double s) {
 __device__ __forceinline__ void report_w(DevErr *e, bool c, uint32_t bit, int slot, int idx, bool count = false) {
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(c);     // the compare's own lane mask
     if (mask == 0ULL) return;
+    // ordered handle (DevErr::map, include/shud_order.h): first_index is the lowest index in the CALLER's numbering, so
+    // the wave's flagged lanes map their indices and the minimum over them is taken (a scalar walk over the mask:
+    // only flagged, hence active, lanes are read).  Plain handles (map == nullptr) pay one uniform load, here only
+    const int *map = __atomic_load_n(&e->map, __ATOMIC_RELAXED);
+    if (map) {
+        const int mine = c ? map[idx] : 0x7fffffff;
+        int best = 0x7fffffff;
+        for (unsigned long long m = mask; m; m &= m - 1ULL) {
+            const int v = __builtin_amdgcn_readlane(mine, __ffsll((long long)m) - 1);
+            best = v < best ? v : best;
+        }
+        idx = best;
+    }
     if ((int)__lane_id() == __ffsll((long long)mask) - 1) {
         if (!(__atomic_load_n(&e->flags, __ATOMIC_RELAXED) & bit)) atomicOr(&e->flags, bit);
         if (__atomic_load_n(&e->first_index[slot], __ATOMIC_RELAXED) > idx) atomicMin(&e->first_index[slot], idx);

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "shud_handle.h"
+#include "shud_order.h"
 #include "shud_tables.h"
 
 using namespace shud;
@@ -53,6 +54,7 @@ int shud_reset_err(shud_rhs *h) {
     for (int k = 0; k < 8; k++) z.first_index[k] = INT_MAX;
     z.n_warn = 0;
     z.warn = h->d_warn;
+    z.map = h->ordered ? h->d_perm : nullptr;
     HIP_TRY(hipMemsetAsync(h->d_warn, 0, kWarnSlots * kWarnStride * sizeof(unsigned long long), h->stream));
     HIP_TRY(hipMemcpyAsync(h->d_err, &z, sizeof(DevErr), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -245,6 +247,77 @@ extern "C" int shud_rhs_create(const ShudMeshSoA *mesh, const ShudParamsSoA *par
     return SHUD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// ordered handles (include/shud_order.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int shud_rhs_create_ordered(const ShudMeshSoA *mesh, const ShudParamsSoA *par, const ShudRhsOptions *opt,
+                                       int kind, const int32_t *user_perm, shud_rhs_t *out) {
+    if (!mesh || !par || !out) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (kind == SHUD_ORDER_IDENTITY) return shud_rhs_create(mesh, par, opt, out);
+    const int NE = mesh->num_ele;
+    if (NE < 0) return shud_fail(SHUD_ERR_ARG, "negative num_ele");
+    std::vector<int> perm((size_t)NE);
+    int rc = shud_order_plan(mesh, kind, user_perm, perm.data());
+    if (rc) return rc;
+    shud_ordered_t store = nullptr;
+    ShudMeshSoA pm;
+    ShudParamsSoA pp;
+    if ((rc = shud_order_apply(mesh, par, perm.data(), &store, &pm, &pp))) return rc;    // refuses lake models
+    shud_rhs *h = new shud_rhs();
+    rc = build(h, &pm, &pp, opt, nullptr);
+    shud_order_free(store);
+    if (!rc) {
+        h->order_kind = kind;
+        h->inv.resize((size_t)NE);
+        for (int k = 0; k < NE; k++) h->inv[perm[k]] = k;
+        h->perm.swap(perm);
+        bool ident = true;               // an identity plan: nothing to carry, the handle behaves as a plain one
+        for (int k = 0; k < NE && ident; k++) ident = h->perm[k] == k;
+        h->ordered = !ident;
+    }
+    if (!rc && h->ordered) {
+        if (!(rc = h->dalloc(&h->d_perm, (size_t)NE)) && !(rc = h->dalloc(&h->d_inv, (size_t)NE)) &&
+            !(rc = h->dalloc(&h->d_stage, 3 * (size_t)NE + h->NR + h->NL))) {
+            hipError_t e = hipMemcpy(h->d_perm, h->perm.data(), (size_t)NE * sizeof(int), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(h->d_inv, h->inv.data(), (size_t)NE * sizeof(int), hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = shud_fail(SHUD_ERR_HIP, "order upload failed: %s", hipGetErrorString(e));
+        }
+        if (!rc) rc = shud_reset_err(h);             // the error word now carries the index map (DevErr::map)
+    }
+    if (rc) { destroy_handle(h); return rc; }
+    *out = h;
+    return SHUD_OK;
+}
+
+extern "C" int shud_rhs_order(shud_rhs_t h, int *kind, int32_t *perm_host, int32_t *inv_host) {
+    if (!h) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (kind) *kind = h->order_kind;
+    const bool have = !h->perm.empty();
+    for (int k = 0; k < h->NE; k++) {
+        if (perm_host) perm_host[k] = have ? h->perm[k] : k;
+        if (inv_host) inv_host[k] = have ? h->inv[k] : k;
+    }
+    return SHUD_OK;
+}
+
+extern "C" int shud_rhs_permute(shud_rhs_t h, int dir, int what, const double *d_src, double *d_dst) {
+    if (!h || !d_src || !d_dst || d_src == d_dst) return shud_fail(SHUD_ERR_ARG, "shud_rhs_permute: bad pointers");
+    if ((dir != SHUD_PERM_TO_INTERNAL && dir != SHUD_PERM_TO_CALLER) || what < SHUD_PERM_STATE || what > SHUD_PERM_ELE3)
+        return shud_fail(SHUD_ERR_ARG, "shud_rhs_permute: bad dir / what");
+    HIP_TRY(hipSetDevice(h->device));
+    const int planes = what == SHUD_PERM_ELE ? 1 : 3;
+    const int ne = what == SHUD_PERM_STATE ? h->n_own : h->NE;
+    const int ntail = what == SHUD_PERM_STATE ? h->n_own_riv + h->NL : 0;
+    if (!h->ordered) {
+        const size_t n = (size_t)planes * ne + ntail;
+        if (n) HIP_TRY(hipMemcpyAsync(d_dst, d_src, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return SHUD_OK;
+    }
+    launch_perm_kernel(dir == SHUD_PERM_TO_INTERNAL ? h->d_perm : h->d_inv, ne, planes, d_src, d_dst, ntail, h->stream);
+    HIP_TRY(hipGetLastError());
+    return SHUD_OK;
+}
+
 extern "C" int shud_rhs_nccl_unique_id(char out[128]) {
     ncclUniqueId id;
     NCCL_TRY(ncclGetUniqueId(&id));
@@ -275,6 +348,22 @@ extern "C" int shud_rhs_destroy(shud_rhs_t h) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int shud_rhs_set_step_inputs(shud_rhs_t h, const ShudStepInputs *in) {
     if (!h || !in) return shud_fail(SHUD_ERR_ARG, "null argument");
+    // ordered handle: the caller's [NE] arrays gathered into the internal numbering on the host, then as below
+    ShudStepInputs g;
+    std::vector<std::vector<double>> gbuf;
+    if (h->ordered) {
+        g = *in;
+        const double **f[] = {&g.net_prep, &g.pot_evap, &g.pot_tran, &g.etp, &g.lai, &g.fu_surf, &g.fu_sub,
+                              &g.e_ic, &g.u_satn, &g.ugw_stale, &g.prcp};
+        for (auto pp : f) {
+            if (!*pp) continue;
+            gbuf.emplace_back((size_t)h->NE);
+            int rc = shud_order_gather_host(h->perm.data(), h->NE, sizeof(double), 1, *pp, gbuf.back().data());
+            if (rc) return rc;
+            *pp = gbuf.back().data();
+        }
+        in = &g;
+    }
     HIP_TRY(hipSetDevice(h->device));
     const size_t nb = (size_t)h->NE * sizeof(double);
     // packed layout: carried-state overrides go through SoA staging slot 0, then into the packed record
@@ -477,10 +566,22 @@ extern "C" int shud_rhs_eval(shud_rhs_t h, double t, const double *y, double *yd
     if (where == SHUD_WHERE_DEVICE) return eval_device(h, t, y, ydot);
     if (where != SHUD_WHERE_HOST) return shud_fail(SHUD_ERR_ARG, "bad where");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->d_y, y, ny * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // ordered handle: y lands in the caller-numbered stage, one permute launch carries it into d_y; ydot goes back
+    // through the same stage before its D2H copy
+    const int ntail = h->n_own_riv + h->NL;
+    HIP_TRY(hipMemcpyAsync(h->ordered ? h->d_stage : h->d_y, y, ny * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (h->ordered) {
+        launch_perm_kernel(h->d_perm, h->NE, 3, h->d_stage, h->d_y, ntail, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
     int rc = eval_device(h, t, h->d_y, h->d_ydot);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ydot, h->d_ydot, ny * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (h->ordered) {
+        launch_perm_kernel(h->d_inv, h->NE, 3, h->d_ydot, h->d_stage, ntail, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(ydot, h->ordered ? h->d_stage : h->d_ydot, ny * sizeof(double), hipMemcpyDeviceToHost,
+                           h->stream));
     if (h->check_errors) {
         if ((rc = read_err(h))) return rc;
         if (h->h_err->flags & kFatal) return shud_fail(SHUD_ERR_PHYSICS, "physics error flags 0x%x", h->h_err->flags);
@@ -519,7 +620,7 @@ extern "C" int shud_rhs_get_error(shud_rhs_t h, ShudErr *e) {
     HIP_TRY(hipSetDevice(h->device));
     int rc = read_err(h);
     if (rc) return rc;
-    const DevErr &d = *h->h_err;
+    const DevErr &d = *h->h_err;         // an ordered handle's kernels recorded the caller's indices (DevErr::map)
     memset(e, 0, sizeof(*e));
     e->flags = d.flags;
     for (int k = 0; k < 8; k++) e->first_index[k] = (d.first_index[k] == INT_MAX) ? -1 : d.first_index[k];
@@ -620,26 +721,36 @@ extern "C" int shud_rhs_sync_diagnostics(shud_rhs_t h, ShudFluxOut *o) {
     int rc = shud_diag_replay(h);
     if (rc) return rc;
     const size_t NE = h->NE, NR = h->NR, NS = h->NS;
-    auto get = [&](double *dst, const double *src, size_t n) -> int {
-        if (dst && n) HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    // planes: 1 = an [NE] array, 3 = a [3*NE] edge-major array (an ordered handle carries these to the caller's
+    // numbering through the stage; the stream is in order, so the stage is free again once the copy before it has
+    // run); 0 = per reach or per lake, copied as it is
+    auto get = [&](double *dst, const double *src, size_t n, int planes) -> int {
+        if (!dst || !n) return 0;
+        if (h->ordered && planes) {
+            launch_perm_kernel(h->d_inv, h->NE, planes, src, h->d_stage, 0, h->stream);
+            HIP_TRY(hipGetLastError());
+            src = h->d_stage;
+        }
+        HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         return 0;
     };
     const DevDiag &g = h->dd;
-    if ((rc = get(o->qele_surf, g.qele_surf, 3 * NE)) || (rc = get(o->qele_sub, g.qele_sub, 3 * NE)) ||
-        (rc = get(o->qele_surf_tot, g.qele_surf_tot, NE)) || (rc = get(o->qele_sub_tot, g.qele_sub_tot, NE)) ||
-        (rc = get(o->q_infil, g.q_infil, NE)) || (rc = get(o->q_exfil, g.q_exfil, NE)) ||
-        (rc = get(o->q_recharge, g.q_recharge, NE)) || (rc = get(o->q_es, g.q_es, NE)) ||
-        (rc = get(o->q_eu, g.q_eu, NE)) || (rc = get(o->q_eg, g.q_eg, NE)) || (rc = get(o->q_tu, g.q_tu, NE)) ||
-        (rc = get(o->q_tg, g.q_tg, NE)) || (rc = get(o->q_eta, g.q_eta, NE)) || (rc = get(o->e_ic, g.e_ic, NE)) ||
-        (rc = get(o->u_satn, g.u_satn, NE)) || (rc = get(o->i_beta, g.i_beta, NE)) ||
-        (rc = get(o->eff_kh, g.eff_kh, NE)) || (rc = get(o->qe2r_surf, g.qe2r_surf, NE)) ||
-        (rc = get(o->qe2r_sub, g.qe2r_sub, NE)) || (rc = get(o->qriv_down, g.qriv_down, NR)) ||
-        (rc = get(o->qriv_up, g.qriv_up, NR)) || (rc = get(o->qriv_surf, g.qriv_surf, NR)) ||
-        (rc = get(o->qriv_sub, g.qriv_sub, NR)) || (rc = get(o->q_lake_surf, g.q_lake_surf, h->NL)) ||
-        (rc = get(o->q_lake_sub, g.q_lake_sub, h->NL)) || (rc = get(o->q_lake_rivin, g.q_lake_rivin, h->NL)) ||
-        (rc = get(o->q_lake_evap, g.q_lake_evap, h->NL)) || (rc = get(o->q_lake_prcp, g.q_lake_prcp, h->NL)) ||
-        (rc = get(o->lake_toparea, g.lake_toparea, h->NL)))
-        return rc;
+    const size_t NL = h->NL;
+    struct { double *dst; const double *src; size_t n; int planes; } arrs[] = {
+        {o->qele_surf, g.qele_surf, 3 * NE, 3}, {o->qele_sub, g.qele_sub, 3 * NE, 3},
+        {o->qele_surf_tot, g.qele_surf_tot, NE, 1}, {o->qele_sub_tot, g.qele_sub_tot, NE, 1},
+        {o->q_infil, g.q_infil, NE, 1}, {o->q_exfil, g.q_exfil, NE, 1}, {o->q_recharge, g.q_recharge, NE, 1},
+        {o->q_es, g.q_es, NE, 1}, {o->q_eu, g.q_eu, NE, 1}, {o->q_eg, g.q_eg, NE, 1}, {o->q_tu, g.q_tu, NE, 1},
+        {o->q_tg, g.q_tg, NE, 1}, {o->q_eta, g.q_eta, NE, 1}, {o->e_ic, g.e_ic, NE, 1}, {o->u_satn, g.u_satn, NE, 1},
+        {o->i_beta, g.i_beta, NE, 1}, {o->eff_kh, g.eff_kh, NE, 1}, {o->qe2r_surf, g.qe2r_surf, NE, 1},
+        {o->qe2r_sub, g.qe2r_sub, NE, 1},
+        {o->qriv_down, g.qriv_down, NR, 0}, {o->qriv_up, g.qriv_up, NR, 0}, {o->qriv_surf, g.qriv_surf, NR, 0},
+        {o->qriv_sub, g.qriv_sub, NR, 0},
+        {o->q_lake_surf, g.q_lake_surf, NL, 0}, {o->q_lake_sub, g.q_lake_sub, NL, 0},
+        {o->q_lake_rivin, g.q_lake_rivin, NL, 0}, {o->q_lake_evap, g.q_lake_evap, NL, 0},
+        {o->q_lake_prcp, g.q_lake_prcp, NL, 0}, {o->lake_toparea, g.lake_toparea, NL, 0}};
+    for (const auto &a : arrs)
+        if ((rc = get(a.dst, a.src, a.n, a.planes))) return rc;
     std::vector<double> tmp;
     if (o->qseg_surf || o->qseg_sub) tmp.resize(std::max<size_t>(NS, 1));
     HIP_TRY(hipStreamSynchronize(h->stream));

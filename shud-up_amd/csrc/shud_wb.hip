@@ -456,6 +456,9 @@ extern "C" int shud_wb_create(shud_rhs_t h, const ShudMeshSoA *m, const ShudPara
     if (h->mode != SHUD_MODE_SERIAL)
         return shud_fail(SHUD_ERR_UNSUPPORTED, "shud_wb: OMP-semantics handles are not supported (the per-element ET "
                                                "terms exist only in the serial path)");
+    if (h->ordered)
+        return shud_fail(SHUD_ERR_UNSUPPORTED, "shud_wb: ordered handles are not supported (the basin sums would run in "
+                                               "another element order, include/shud_order.h)");
     if (h->lakeon || m->num_lake > 0)
         return shud_fail(SHUD_ERR_UNSUPPORTED, "shud_wb: lake models are not supported (the reference's diagnostic "
                                                "ignores lake storage)");

@@ -1,7 +1,8 @@
 // shud_gpu.cpp — C++ host of the device path: SHUD() (src/Model/shud.cpp:32-170) with the RHS, the ET-step
 // prelude, the integrator and the outputs on one MI355X, driven through the C-ABIs of include/.
 //
-//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] <input_dir> <project>
+//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] [--reorder bfs]
+//            <input_dir> <project>
 //   shud_gpu --rhs-check K | --rhs-bench [--evals N] ...   partitioned RHS modes (shud_gpu_part.cpp)
 //
 // input_dir/<project>.* are the reference's input files (FileIn, IO.cpp:53-91); forcing csv paths in
@@ -34,6 +35,13 @@
 // shud_rhs_summary has already put boundary heads into the device arrays, which the reference's arrays do not hold
 // at that point.  --flood: FloodWarning(t) after ExportResults (shud.cpp:154) on the arrays summary and the
 // diagnostics replay have just filled, into <prj>.flood.csv.
+// --reorder bfs runs the whole device side in the breadth-first element order of include/shud_order.h: the mesh, the
+// parameters, the ET mesh and the initial state (y, IS, snow) are carried into it by the appliers and the handles are
+// plain ones (the device ET prelude writes the step inputs straight into the handle, so the device side shares one
+// numbering).  Every file stays in the input's numbering: element outputs are registered with shud_out_add_mapped,
+// restart snapshots with shud_mon_set_ic_order, .cfg.ic.bak comes from the input's own arrays; flood alerts are
+// per reach.  SHUD_WB_DIAG with --reorder is refused (its basin sums would run in another order), and so are lake
+// models.  Without the flag the program makes exactly the calls it made before.
 // Not restated (out of the device path's scope): the screen print, NetCDF forcing and outputs, the uncoupled -g
 // mode.
 #include <strings.h>
@@ -52,6 +60,7 @@
 #include "shud_host.h"
 #include "shud_mon.h"
 #include "shud_ode.h"
+#include "shud_order.h"
 #include "shud_out.h"
 #include "shud_rhs.h"
 #include "shud_wb.h"
@@ -60,12 +69,14 @@ static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 
 static void usage() {
     fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots]\n"
-                    "                <input_dir> <project>\n"
+                    "                [--reorder bfs] <input_dir> <project>\n"
                     "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n"
                     "  --flood         write <outdir>/<project>.flood.csv (reaches above their bank after each solver step)\n"
                     "  --ic-snapshots  write <outdir>/<project>.cfg.ic.bak and, every Update_IC_STEP minutes and at the\n"
                     "                  end, <outdir>/<project>.cfg.ic.update (restart file for INIT_MODE 3)\n"
-                    "  Both are off by default (the reference always writes these files).\n");
+                    "  Both are off by default (the reference always writes these files).\n"
+                    "  --reorder bfs   run the device side in a breadth-first element order (neighbours close in memory);\n"
+                    "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n");
 }
 
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
@@ -92,6 +103,19 @@ static bool env_truthy(const char *s) {
     return true;
 }
 
+// the SHUD_ARR_* arrays indexed by element (the others are per reach or per lake)
+static bool arr_is_ele(int a) {
+    switch (a) {
+        case SHUD_ARR_Y_RIV_STG: case SHUD_ARR_Y_LAKE_STG: case SHUD_ARR_QRIV_DOWN: case SHUD_ARR_QRIV_UP:
+        case SHUD_ARR_QRIV_SURF: case SHUD_ARR_QRIV_SUB: case SHUD_ARR_LAKE_TOPAREA: case SHUD_ARR_Q_LAKE_EVAP:
+        case SHUD_ARR_Q_LAKE_PRCP: case SHUD_ARR_Q_LAKE_RIVIN: case SHUD_ARR_Q_LAKE_RIVOUT: case SHUD_ARR_Q_LAKE_SURF:
+        case SHUD_ARR_Q_LAKE_SUB:
+            return false;
+        default:
+            return true;
+    }
+}
+
 static const char *lonlat_name(int m) { return m == 1 ? "FORCING_MEAN" : (m == 2 ? "FIXED" : "FORCING_FIRST"); }
 
 int main(int argc, char **argv) {
@@ -101,6 +125,7 @@ int main(int argc, char **argv) {
     bool quiet = false;
     int rhs_check = 0, evals = 0;
     bool rhs_bench = false, want_flood = false, want_ic = false;
+    std::string reorder;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -113,6 +138,7 @@ int main(int argc, char **argv) {
         else if (a == "--rhs-bench") rhs_bench = true;
         else if (a == "--flood") want_flood = true;
         else if (a == "--ic-snapshots") want_ic = true;
+        else if (a == "--reorder" && i + 1 < argc) reorder = argv[++i];
         else if (a == "--evals" && i + 1 < argc) evals = atoi(argv[++i]);
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else pos.push_back(argv[i]);
@@ -120,6 +146,15 @@ int main(int argc, char **argv) {
     if (pos.size() != 2) { usage(); return 1; }
     const char *indir = pos[0], *prj = pos[1];
     if (outdir.empty()) outdir = std::string("output/") + prj + ".out";
+    if (!reorder.empty() && reorder != "bfs") {
+        fprintf(stderr, "--reorder: unknown order '%s' (bfs)\n", reorder.c_str());
+        return 1;
+    }
+    if (!reorder.empty() && env_truthy(getenv("SHUD_WB_DIAG"))) {
+        fprintf(stderr, "--reorder cannot be combined with SHUD_WB_DIAG: the water-balance sums over the basin would "
+                        "run in another element order\n");
+        return 1;
+    }
     const auto wall0 = std::chrono::steady_clock::now();
 
     // ---- loadinput + initialize + LoadIC (shud.cpp:49-64) ----
@@ -143,6 +178,46 @@ int main(int argc, char **argv) {
     const double *y0 = shud_project_array(p, "y0", &ny);
     const double *y_is = shud_project_array(p, "y_is", nullptr);
     const double *y_snow = shud_project_array(p, "y_snow", nullptr);
+    // the input's own arrays: what .cfg.ic.bak and the first snapshot are written from, in the input's numbering
+    const double *const y0_in = y0, *const y_is_in = y_is, *const y_snow_in = y_snow;
+    // ---- --reorder: the model, the ET mesh and the initial state in the planned element order ----
+    std::vector<int32_t> perm, inv;
+    shud_ordered_t ordered = nullptr;
+    std::vector<std::vector<int32_t>> o_int;
+    std::vector<std::vector<double>> o_dbl;
+    // a per-element host array (then `tail` more values, copied) carried into the planned order
+    auto gi = [&](const int32_t *&a) {
+        if (!a) return;
+        o_int.emplace_back(perm.size());
+        shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(int32_t), 1, a, o_int.back().data());
+        a = o_int.back().data();
+    };
+    auto gd = [&](const double *&a, int planes, size_t tail) {
+        if (!a) return;
+        const size_t n = (size_t)planes * perm.size();
+        o_dbl.emplace_back(n + tail);
+        shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(double), planes, a, o_dbl.back().data());
+        std::copy(a + n, a + n + tail, o_dbl.back().begin() + n);
+        a = o_dbl.back().data();
+    };
+    if (!reorder.empty()) {
+        const int ne = mesh.num_ele;
+        perm.resize((size_t)ne);
+        inv.resize((size_t)ne);
+        ShudMeshSoA pm;
+        ShudParamsSoA pp;
+        if (shud_order_plan(&mesh, SHUD_ORDER_BFS, nullptr, perm.data()) ||
+            shud_order_apply(&mesh, &par, perm.data(), &ordered, &pm, &pp)) {
+            fprintf(stderr, "--reorder: %s\n", shud_rhs_last_error_string());
+            return 1;
+        }
+        mesh = pm;
+        par = pp;
+        for (int k = 0; k < ne; k++) inv[perm[k]] = k;
+        gd(y0, 3, (size_t)(ny - 3 * (int64_t)ne));
+        gd(y_is, 1, 0);
+        gd(y_snow, 1, 0);
+    }
     if (!quiet)
         printf("* \t Project: %s  NumEle %d  NumRiv %d  NumSeg %d  NumLake %d  NY %lld\n"
                "* \t StartTime %.1f  EndTime %.1f [min]  SolverStep %.1f  ETStep %.1f  NumSteps %lld\n",
@@ -159,6 +234,11 @@ int main(int argc, char **argv) {
     ShudEtMeshSoA etm;
     ShudEtParams etp;
     shud_project_et(p, &etm, &etp);
+    if (!perm.empty()) {
+        gi(etm.iforc); gi(etm.ilc); gi(etm.imf); gi(etm.ilake);
+        gd(etm.z_surf, 1, 0); gd(etm.albedo, 1, 0); gd(etm.fix_pressure, 1, 0); gd(etm.wind_h, 1, 0);
+        gd(etm.veg_frac, 1, 0); gd(etm.nx, 1, 0); gd(etm.ny, 1, 0); gd(etm.nz, 1, 0);
+    }
     if (shud_et_attach(h, &etm, &etp) || shud_et_set_state(h, y_is, y_snow)) {
         fprintf(stderr, "shud_et_attach: %s\n", shud_rhs_last_error_string());
         return 1;
@@ -209,7 +289,14 @@ int main(int argc, char **argv) {
         ShudPrintSpec ps = {d.basename, src, d.n_all, d.flag_io, d.interval, d.iflux, (int64_t)c.forc_start_time,
                             c.binary, c.ascii, c.radiation_input_mode, c.terrain_radiation,
                             lonlat_name(c.solar_lonlat_mode), c.solar_lon_deg, c.solar_lat_deg};
-        if (shud_out_add(out, &ps)) {
+        // --reorder: column c of an element output reads the internal element inv[c]
+        const bool mapped = !inv.empty() && arr_is_ele(d.array) && d.n_all == mesh.num_ele;
+        if (!inv.empty() && arr_is_ele(d.array) && !mapped) {
+            fprintf(stderr, "--reorder: element output %s has %d columns, mesh %d elements\n", d.basename, d.n_all,
+                    mesh.num_ele);
+            return 1;
+        }
+        if (mapped ? shud_out_add_mapped(out, &ps, inv.data()) : shud_out_add(out, &ps)) {
             fprintf(stderr, "shud_out_add(%s): %s\n", d.basename, shud_rhs_last_error_string());
             return 1;
         }
@@ -245,8 +332,9 @@ int main(int argc, char **argv) {
     const int NE = mesh.num_ele, NR = mesh.num_riv, NL = mesh.num_lake;
     // LoadIC's values through the device-free formatter (what the reference's arrays hold before the first step)
     auto ic_from_host = [&](const std::string &fn, double th) {
-        return shud_mon_write_ic_host(fn.c_str(), th, NE, NR, NL, y_is, y_snow, y0, y0 + NE, y0 + 2 * (size_t)NE,
-                                      y0 + 3 * (size_t)NE, NL ? y0 + 3 * (size_t)NE + NR : nullptr);
+        return shud_mon_write_ic_host(fn.c_str(), th, NE, NR, NL, y_is_in, y_snow_in, y0_in, y0_in + NE,
+                                      y0_in + 2 * (size_t)NE, y0_in + 3 * (size_t)NE,
+                                      NL ? y0_in + 3 * (size_t)NE + NR : nullptr);
     };
     long long ic_snaps = 0;
     if (want_flood || want_ic) {
@@ -268,7 +356,7 @@ int main(int argc, char **argv) {
                              shud_rhs_device_array(h, SHUD_ARR_Y_ELE_GW, nullptr),
                              shud_rhs_device_array(h, SHUD_ARR_Y_RIV_STG, nullptr),
                              NL ? shud_rhs_device_array(h, SHUD_ARR_Y_LAKE_STG, nullptr) : nullptr};
-            if (shud_mon_add_ic(mon, &is)) {
+            if (shud_mon_add_ic(mon, &is) || (!perm.empty() && shud_mon_set_ic_order(mon, perm.data()))) {
                 fprintf(stderr, "shud_mon_add_ic: %s\n", shud_rhs_last_error_string());
                 return 1;
             }
@@ -501,6 +589,7 @@ int main(int argc, char **argv) {
     shud_rhs_device_free(h, d_y);
     if (d_du) shud_rhs_device_free(h, d_du);
     shud_rhs_destroy(h);
+    if (ordered) shud_order_free(ordered);
     shud_project_free(p);
     return rc;
 }

@@ -243,6 +243,7 @@ OUT_FUNCTIONS = {
     "shud_rhs_device_array": (C.c_void_p, [_H, C.c_int, C.POINTER(C.c_int64)]),
     "shud_out_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(_H)]),
     "shud_out_add": (C.c_int, [_H, C.POINTER(ShudPrintSpec)]),
+    "shud_out_add_mapped": (C.c_int, [_H, C.POINTER(ShudPrintSpec), c_int32_p]),
     "shud_out_export": (C.c_int, [_H, C.c_double]),
     "shud_out_rows": (C.c_int64, [_H, C.c_int]),
     "shud_out_flush": (C.c_int, [_H]),
@@ -309,6 +310,7 @@ MON_FUNCTIONS = {
     "shud_mon_flood_rows": (C.c_int64, [_H]),
     "shud_mon_flood_last": (C.c_int, [_H]),
     "shud_mon_add_ic": (C.c_int, [_H, C.POINTER(ShudIcSpec)]),
+    "shud_mon_set_ic_order": (C.c_int, [_H, c_int32_p]),
     "shud_mon_ic_update": (C.c_int, [_H, C.c_double]),
     "shud_mon_ic_snapshots": (C.c_int64, [_H]),
     "shud_mon_flush": (C.c_int, [_H]),
@@ -322,11 +324,28 @@ MON_FUNCTIONS = {
 }
 
 
+# ---- include/shud_order.h (element locality ordering) ----
+SHUD_ORDER_IDENTITY, SHUD_ORDER_USER, SHUD_ORDER_BFS = 0, 1, 2
+SHUD_PERM_TO_INTERNAL, SHUD_PERM_TO_CALLER = 0, 1
+SHUD_PERM_STATE, SHUD_PERM_ELE, SHUD_PERM_ELE3 = 0, 1, 2
+ORDER_FUNCTIONS = {
+    "shud_order_plan": (C.c_int, [C.POINTER(ShudMeshSoA), C.c_int, c_int32_p, c_int32_p]),
+    "shud_order_apply": (C.c_int, [C.POINTER(ShudMeshSoA), C.POINTER(ShudParamsSoA), c_int32_p, C.POINTER(_H),
+                                   C.POINTER(ShudMeshSoA), C.POINTER(ShudParamsSoA)]),
+    "shud_order_free": (C.c_int, [_H]),
+    "shud_order_gather_host": (C.c_int, [c_int32_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p]),
+    "shud_rhs_create_ordered": (C.c_int, [C.POINTER(ShudMeshSoA), C.POINTER(ShudParamsSoA), C.POINTER(ShudRhsOptions),
+                                          C.c_int, c_int32_p, C.POINTER(_H)]),
+    "shud_rhs_order": (C.c_int, [_H, C.POINTER(C.c_int), c_int32_p, c_int32_p]),
+    "shud_rhs_permute": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
+
 def bind(lib, strict=True):
     """set the signatures; strict=False (A/B builds of older sources) skips symbols the library lacks"""
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
                               + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())
-                              + list(MON_FUNCTIONS.items())):
+                              + list(MON_FUNCTIONS.items()) + list(ORDER_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

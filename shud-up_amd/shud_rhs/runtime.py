@@ -40,13 +40,29 @@ def _check(rc, what):
 
 class RhsHandle:
     def __init__(self, model, mode=abi.SHUD_MODE_SERIAL, device=0, stream=None, check_errors=True,
-                 partition=None):
+                 partition=None, order=None):
+        """order (include/shud_order.h): None = a plain handle; "identity", "bfs" or a permutation array (new
+        element k is old order[k]) = shud_rhs_create_ordered.  Host arrays stay in the model's numbering, device
+        pointers are in the internal one (permute())."""
         self.model = model
+        self.ordered = False
         self._mesh = model.mesh_struct()
         self._par = model.params_struct()
         opt = abi.ShudRhsOptions(mode, device, stream, 1 if check_errors else 0)
         h = C.c_void_p()
-        if partition is None:
+        if order is not None:
+            if partition is not None:
+                raise ValueError("order= is not available on partitioned handles")
+            kind, up = order_kind(order, model.num_ele)
+            _check(lib().shud_rhs_create_ordered(C.byref(self._mesh), C.byref(self._par), C.byref(opt), kind,
+                                                 None if up is None else up.ctypes.data_as(abi.c_int32_p),
+                                                 C.byref(h)), "shud_rhs_create_ordered")
+            self.n_own, self.n_own_riv = model.num_ele, model.num_riv
+            self.n_lake = getattr(model, "num_lake", 0)
+            self.h = h
+            perm = self.order()[1]
+            self.ordered = bool((perm != np.arange(perm.size)).any())    # device pointers are in another numbering
+        elif partition is None:
             _check(lib().shud_rhs_create(C.byref(self._mesh), C.byref(self._par), C.byref(opt), C.byref(h)),
                    "shud_rhs_create")
             self.n_own, self.n_own_riv = model.num_ele, model.num_riv
@@ -126,6 +142,21 @@ class RhsHandle:
         if sh.value:
             out["shared_edges"] = sh.value
         return out
+
+    def order(self):
+        """(kind, perm, inv): abi.SHUD_ORDER_*, perm[internal] = model index, inv[model index] = internal"""
+        kind = C.c_int()
+        perm, inv = (np.zeros(self.model.num_ele, dtype=np.int32) for _ in range(2))
+        _check(lib().shud_rhs_order(self.h, C.byref(kind), perm.ctypes.data_as(abi.c_int32_p),
+                                    inv.ctypes.data_as(abi.c_int32_p)), "shud_rhs_order")
+        return kind.value, perm, inv
+
+    def permute(self, d_src, d_dst, to="internal", what="state"):
+        """stream-ordered device copy between the numberings (shud_rhs_permute): to = "internal" | "caller";
+        what = "state" ([sf|us|gw|riv]), "ele" ([NE]) or "ele3" ([3*NE] edge-major)"""
+        d = {"internal": abi.SHUD_PERM_TO_INTERNAL, "caller": abi.SHUD_PERM_TO_CALLER}[to]
+        w = {"state": abi.SHUD_PERM_STATE, "ele": abi.SHUD_PERM_ELE, "ele3": abi.SHUD_PERM_ELE3}[what]
+        _check(lib().shud_rhs_permute(self.h, d, w, C.c_void_p(d_src), C.c_void_p(d_dst)), "shud_rhs_permute")
 
     def diagnostics(self):
         m = self.model
@@ -248,6 +279,73 @@ class RhsHandle:
                                          1 if publish else 0, float(timeout_ms)), "debug_halo")
 
 
+def order_kind(order, num_ele):
+    """(SHUD_ORDER_*, user permutation or None) of an order= argument: "identity", "bfs" or a permutation array"""
+    if isinstance(order, str):
+        try:
+            return {"identity": abi.SHUD_ORDER_IDENTITY, "bfs": abi.SHUD_ORDER_BFS}[order], None
+        except KeyError:
+            raise ValueError(f"unknown order {order!r}") from None
+    up = np.ascontiguousarray(order, dtype=np.int32)
+    if up.shape != (num_ele,):
+        raise ValueError(f"order has shape {up.shape}, expected ({num_ele},)")
+    return abi.SHUD_ORDER_USER, up
+
+
+def order_plan(model, order):
+    """perm [NE] (new element k is old perm[k]) that shud_rhs_create_ordered would use (shud_order_plan; no device)"""
+    kind, up = order_kind(order, model.num_ele)
+    mesh = model.mesh_struct()
+    perm = np.zeros(model.num_ele, dtype=np.int32)
+    _check(lib().shud_order_plan(C.byref(mesh), kind, None if up is None else up.ctypes.data_as(abi.c_int32_p),
+                                 perm.ctypes.data_as(abi.c_int32_p)), "shud_order_plan")
+    return perm
+
+
+def order_gather(perm, a, planes=1):
+    """a per-element host array carried into the numbering of perm (shud_order_gather_host)"""
+    perm = np.ascontiguousarray(perm, dtype=np.int32)
+    a = np.ascontiguousarray(a)
+    out = np.empty_like(a)
+    assert a.size == planes * perm.size
+    _check(lib().shud_order_gather_host(perm.ctypes.data_as(abi.c_int32_p), perm.size, a.itemsize, int(planes),
+                                        a.ctypes.data, out.ctypes.data), "shud_order_gather_host")
+    return out
+
+
+def order_apply(model, perm):
+    """the model under perm (shud_order_apply: mesh and parameters; the step arrays through shud_order_gather_host),
+    as a new ShudModel that owns its arrays.  Lake models raise (SHUD_ERR_UNSUPPORTED)."""
+    import copy
+
+    from .model import ELE1, ELE3
+    perm = np.ascontiguousarray(perm, dtype=np.int32)
+    mesh, par = model.mesh_struct(), model.params_struct()
+    mo, po, st = abi.ShudMeshSoA(), abi.ShudParamsSoA(), C.c_void_p()
+    _check(lib().shud_order_apply(C.byref(mesh), C.byref(par), perm.ctypes.data_as(abi.c_int32_p), C.byref(st),
+                                  C.byref(mo), C.byref(po)), "shud_order_apply")
+    try:
+        NE = model.num_ele
+
+        def take(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if ptr and n else (np.zeros(0) if ptr else None)
+
+        r = copy.deepcopy(model)                    # reaches, segments, tables, meta: unchanged
+        r.nabr = take(mo.nabr, 3 * NE)
+        for k in ELE1 + ELE3:
+            if k in model.ele:
+                r.ele[k] = take(getattr(mo, k), (3 if k in ELE3 else 1) * NE)
+        for k in ("ibc", "iss", "ilake"):
+            if getattr(model, k) is not None:
+                setattr(r, k, take(getattr(mo, k), NE))
+        r.seg_ele = take(mo.seg_ele, model.num_seg) if model.num_seg else model.seg_ele.copy()
+        r.par = {k: take(getattr(po, k), NE) for k in abi.PARAM_NAMES}
+        r.step = {k: order_gather(perm, v) for k, v in model.step.items()}
+    finally:
+        lib().shud_order_free(st)
+    return r.finalize()
+
+
 def plan_layout(model, mode=abi.SHUD_MODE_SERIAL, partition=None, arrays=False):
     """What RhsHandle(model, mode, partition=partition) would lay out, derived on the host alone
     (shud_rhs_plan_layout): the keys of RhsHandle.layout() plus n_int and riv_sb; arrays=True adds edge_plan [NE]
@@ -362,13 +460,21 @@ class Output:
         self._keep = []
 
     def add(self, basename, d_src, n_all, interval, iflux, start_time=0, flag_io=None, binary=True, ascii=False,
-            radiation_input_mode=0, terrain_radiation=0, solar_lonlat_mode="FORCING_FIRST", lon=0.0, lat=0.0):
+            radiation_input_mode=0, terrain_radiation=0, solar_lonlat_mode="FORCING_FIRST", lon=0.0, lat=0.0,
+            col_src=None):
+        """col_src [n_all]: column c reads d_src[col_src[c]] (shud_out_add_mapped); flag_io stays by column c"""
         flags = None if flag_io is None else np.ascontiguousarray(flag_io, dtype=np.int32)
+        cmap = None if col_src is None else np.ascontiguousarray(col_src, dtype=np.int32)
+        assert cmap is None or cmap.size == int(n_all)
         bn, sm = str(basename).encode(), str(solar_lonlat_mode).encode()
         spec = abi.ShudPrintSpec(bn, C.c_void_p(d_src), int(n_all), None if flags is None else flags.ctypes.data,
                                  int(interval), int(iflux), int(start_time), int(bool(binary)), int(bool(ascii)),
                                  int(radiation_input_mode), int(terrain_radiation), sm, float(lon), float(lat))
-        _check(lib().shud_out_add(self.h, C.byref(spec)), "shud_out_add")
+        if cmap is None:
+            _check(lib().shud_out_add(self.h, C.byref(spec)), "shud_out_add")
+        else:
+            _check(lib().shud_out_add_mapped(self.h, C.byref(spec), cmap.ctypes.data_as(abi.c_int32_p)),
+                   "shud_out_add_mapped")
         self._keep.append((bn, sm, flags))
         return len(self._keep) - 1
 
@@ -538,6 +644,12 @@ class RunMonitors:
         spec = abi.ShudIcSpec(pth, int(update_ic_step), int(n_ele), int(n_riv), int(n_lake), *[_dptr(a) for a in arrs])
         self._keep.append((pth,) + arrs)
         _check(lib().shud_mon_add_ic(self.h, C.byref(spec)), "shud_mon_add_ic")
+
+    def set_ic_order(self, perm):
+        """the snapshot's element arrays are in an internal numbering, perm[k] the file's (0-based) element of source
+        element k (shud_mon_set_ic_order); after add_ic"""
+        p = np.ascontiguousarray(perm, dtype=np.int32)
+        _check(lib().shud_mon_set_ic_order(self.h, p.ctypes.data_as(abi.c_int32_p)), "shud_mon_set_ic_order")
 
     def ic_update(self, t):
         """True when a snapshot was due and queued"""

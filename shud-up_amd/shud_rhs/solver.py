@@ -49,10 +49,15 @@ class ShudSolver:
         self.ode = OdeSolver(handle, ctl.start, y0, ctl.reltol, ctl.abstol, ctl.init_step, ctl.max_step,
                              ctl.min_step, ctl.max_num_steps)
         self.y = None
+        # the handle runs in an internal element order (RhsHandle(order=)): device vectors are carried to the model's
+        self._ordered = getattr(handle, "ordered", False)
         self.quad_steps = 0             # monitor steps of run(quad=True)
 
     def run(self, num_steps, forcing=None, on_output=None, output=None, wb=None, quad=False):
-        """num_steps solver steps (the reference's NumSteps loop); on_output(i, t, y) after each (host copy of y).
+        """On an ordered handle (RhsHandle(order=)) y0 and the y of on_output are in the model's numbering; `output`
+        controls read the handle's device arrays, which are in the internal one (Output.add(col_src=inv)); wb is
+        refused (its basin sums would change order).
+        num_steps solver steps (the reference's NumSteps loop); on_output(i, t, y) after each (host copy of y).
         output: runtime.Output whose controls point at the handle's device arrays — after each solver step
         summary(udata) + ExportResults(t) run on the device (shud.cpp:137,153): no host copy of y at all.
         wb: runtime.WaterBalance (needs output) — the reference's SHUD_WB_DIAG hooks (shud.cpp:110-112,137-152):
@@ -71,6 +76,9 @@ class ShudSolver:
             raise ValueError("wb needs output (the device-resident loop)")
         if quad and wb is None:
             raise ValueError("quad needs wb")
+        ordered = self._ordered
+        if ordered and wb is not None:
+            raise ValueError("water-balance diagnostics are not available on an ordered handle")
         if output is not None:
             d_y = self._out_y = getattr(self, "_out_y", None) or self.h.device_alloc(8 * self.h.num_y)
         d_du = None
@@ -122,7 +130,11 @@ class ShudSolver:
                 output.export(self.t)
             if on_output is not None:
                 if self.y is None:
-                    self.y = self.h.d2h(np.empty(self.h.num_y), d_y)
+                    src = d_y
+                    if ordered:                # d_y is in the internal numbering
+                        src = self._cal_y = getattr(self, "_cal_y", None) or self.h.device_alloc(8 * self.h.num_y)
+                        self.h.permute(d_y, src, to="caller")
+                    self.y = self.h.d2h(np.empty(self.h.num_y), src)
                 on_output(i, self.t, self.y)
         return self.t, self.y
 
@@ -139,7 +151,7 @@ class ShudSolver:
 
     def close(self):
         self.ode.close()
-        for name in ("_out_y", "_wb_du"):
+        for name in ("_out_y", "_wb_du", "_cal_y"):
             if getattr(self, name, None):
                 self.h.device_free(getattr(self, name))
                 setattr(self, name, None)
