@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE ONLY — second, independent restatement of the SHUD RHS in vectorised numpy.
 
 Written separately from shud_oracle.c (different code shape: whole-array expressions instead of the
-reference's per-element loops) so the two restatements cross-check each other; the reference itself
-cannot be compiled here (no SUNDIALS headers) and ships no golden vectors ("parity unpinned").
+reference's per-element loops) so the two restatements cross-check each other; both are also held to the
+reference's own f(), compiled in place (oracle/ref/, tests/test_ref_pin.py; no lakes in this one).
 Same fp64 operation order as the reference, so on identical inputs it must agree with shud_oracle.c
 bit for bit.  Citations are to /root/reference/src.  Serial (`make shud`) and OMP semantics.
 Pure-numpy; sized for meshes up to ~1e5 elements in tests.

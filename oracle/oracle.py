@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE ONLY — ctypes wrapper of oracle/liboracle.so (the CPU restatement in
 shud_oracle.c).  Used by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg as the checker.
-Parity status: "parity unpinned" (see shud_oracle.c header and DESIGN.md §Oracle).
+Parity status: f(), the leaf equations and the ET prelude are pinned to the reference's own code (oracle/ref/,
+tests/test_ref_pin.py); the integrator restatement is not.
 """
 import ctypes as C
 import os

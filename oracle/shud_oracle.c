@@ -5,12 +5,12 @@
  * only as the checker / CPU baseline — never as the product path (which is the HIP library under
  * shud-up_amd/).
  *
- * PARITY STATUS: "parity unpinned".  The reference ships no tests, fixtures or golden vectors for
- * this path, and its RHS cannot be compiled here without SUNDIALS' nvector headers
- * (src/Model/Macros.hpp:163,166 include them unconditionally; SUNDIALS is not installed and writing
- * stand-in headers for it is not allowed).  This file is therefore a line-by-line restatement of the
- * reference algorithm, cited file:line below, cross-checked by an independent numpy restatement
- * (oracle/numpy_oracle.py) and by conservation identities (tests/test_oracle.py).
+ * PARITY STATUS: pinned for f() and the leaf equations.  The reference's own units, compiled in place with a
+ * vector-container stand-in for the SUNDIALS nvector header they include (oracle/ref/), give the
+ * DY this file gives, bit for bit, in serial and OpenMP semantics on ccw, heihe, qhh and a synthetic
+ * boundary-condition project (tests/test_ref_pin.py; recordings under tests/golden/ref/).  This file is a
+ * line-by-line restatement of the reference algorithm, cited file:line below, also cross-checked by an
+ * independent numpy restatement (oracle/numpy_oracle.py) and by conservation identities (tests/test_oracle.py).
  *
  * Structure follows the reference exactly: f_update -> f_loop (loops A,B,C,D + PassValue) ->
  * f_applyDY, with the same fp64 operation order, the reference's own min/max (functions.hpp:117-123,

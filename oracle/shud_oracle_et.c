@@ -7,7 +7,8 @@
  * with the leaf equations of src/Equations/is_sm_et.hpp/.cpp, Equations.hpp:65-72, functions.hpp:191-201 and
  * the per-element _AccTemp queues of src/classes/AccTemperature.hpp (each element keeps its own queue here,
  * as the reference does; the device keeps the shared bookkeeping once).  glibc libm, -ffp-contract=off.
- * Parity unpinned (no reference build): see DESIGN.md §2.
+ * Pinned to the reference's own updateforcing / ET on ccw with the cryosphere on, and its ET leaves to the
+ * reference's (tests/test_et.py, tests/test_kat.py).
  * Deviation, flagged: _AccTemp::ACC is never initialised by the reference's constructor
  * (AccTemperature.hpp:27,41-45); it starts at 0.0 here and on the device. */
 #include <math.h>
@@ -339,4 +340,19 @@ void oracle_et_destroy(OracleEt *E) {
                   E->fu_Surf, E->fu_Sub, E->rn_factor, E->tsr_factor, E->tsr_has, E->acc_surf, E->acc_sub};
     for (size_t k = 0; k < sizeof(ps) / sizeof(ps[0]); k++) free(ps[k]);
     free(E);
+}
+
+/* known-answer entry for the ET leaves (ids 100..102, after oracle_kat's in shud_oracle.c): the functions above
+ * on n input tuples, argument order as the reference declares them (is_sm_et.hpp); tests/test_kat.py holds them
+ * to the reference's own functions (oracle/ref/shud_ref_kat.cpp) on tests/kat_grids.py's grids. */
+int oracle_et_kat(int fn, const double *in, int n, double *out) {
+    const int k = fn == 100 ? 6 : fn == 101 ? 8 : fn == 102 ? 4 : -1;
+    if (k < 0) return -1;
+    for (int t = 0; t < n; t++) {
+        const double *x = in + (size_t)t * k;
+        out[t] = fn == 100 ? PET_PM_openwater(x[0], x[1], x[2], x[3], x[4], x[5])
+               : fn == 101 ? PET_Penman_Monteith(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7])
+                           : AerodynamicResistance(x[0], x[1], x[2], x[3]);
+    }
+    return 0;
 }

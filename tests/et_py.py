@@ -27,6 +27,7 @@ def frozen(T, high, low):                   # functions.hpp:191-201
 class PyAcc:                                # AccTemperature.hpp
     def __init__(self, maxlen):
         self.ts, self.tacc, self.n, self.acc, self.q, self.maxlen = -9999., 0., 0, 0., [], maxlen
+        self.pushes, self.pops, self.n_of_day = 0, 0, []      # bookkeeping for the tests (not the reference's)
 
     def push(self, x, tnow):
         self.tacc += x
@@ -35,8 +36,11 @@ class PyAcc:                                # AccTemperature.hpp
             v = self.tacc / self.n
             self.q.append(v)
             self.acc += v
+            self.pushes += 1
+            self.n_of_day.append(self.n)
             if len(self.q) > self.maxlen:
                 self.acc -= self.q.pop(0)
+                self.pops += 1
             self.tacc, self.n, self.ts = 0., 0, tnow
 
     def get(self):

@@ -10,6 +10,10 @@ import numpy as np
 KAT = dict(MANNING=0, EFFKH=1, WEIR=2, R2E=3, SATK=4, SMS=5, DADY=6, AREA=7, PEREM=8, TOPW=9, TOPAREA=10)
 NIN = [4, 6, 8, 8, 2, 3, 3, 4, 4, 4, 4]
 ZERO, EPSILON, EPS_SLOPE = 1e-10, 0.005, 0.05e-6
+# ET leaves (is_sm_et.hpp / is_sm_et.cpp): ids of oracle_et_kat (oracle/shud_oracle_et.c) and of the reference
+# dispatcher ref_kat (oracle/ref/shud_ref_kat.cpp); the device has no separate entry for them
+ET_KAT = dict(PET_OW=100, PET_PM=101, AERO_RA=102)
+ET_NIN = dict(PET_OW=6, PET_PM=8, AERO_RA=4)
 
 
 def _around(v):
@@ -66,11 +70,28 @@ def grid(name, seed=7):
         rows = list(itertools.product([-50.0, -1e-3, -0.0, 0.0, 1e-9, 2.0, 40.0], [0.0, 1e-3, 5.0, 30.0],
                                       [0.0] + _around(EPS_SLOPE) + [-EPS_SLOPE, 0.5, -0.5, 2.0]))
         rnd = np.column_stack([rng.uniform(-10, 10, 500), rng.uniform(0.1, 40, 500), rng.uniform(-2, 2, 500)])
+    elif name == "PET_OW":         # is_sm_et.cpp:56-63 (Delta, Gamma, lambda, Rad, ed, U2)
+        rows = list(itertools.product([0.0, 0.05, 0.25], [0.0, 0.04, 0.07], [2.43, 2.501], [0.0, 1e-6, 8e-4],
+                                      [0.0, 0.5, 3.0], [0.0, 1e-3, 2.0, 15.0]))     # Delta = Gamma = 0: 0/0 -> NaN
+        rnd = np.column_stack([rng.uniform(0.02, 0.4, 500), rng.uniform(0.03, 0.08, 500), rng.uniform(2.4, 2.55, 500),
+                               rng.uniform(0, 1e-3, 500), rng.uniform(0, 4, 500), rng.uniform(0, 12, 500)])
+    elif name == "PET_PM":         # is_sm_et.cpp:31-55 (Rad, rho, ed, Delta, r_a, r_s, Gamma, lambda)
+        rows = list(itertools.product([0.0, 5e-4], [0.9, 1.25], [0.0, 1.5], [0.0, 0.2], [0.0, 1e-3, 40.0, 1e4],
+                                      [0.0, 50.0, 2e3], [0.0, 0.066], [2.45]))       # r_a = 0: inf / NaN paths
+        rnd = np.column_stack([rng.uniform(0, 1e-3, 500), rng.uniform(0.8, 1.3, 500), rng.uniform(0, 4, 500),
+                               rng.uniform(0.02, 0.4, 500), rng.uniform(1, 500, 500), rng.uniform(40, 4000, 500),
+                               rng.uniform(0.03, 0.08, 500), rng.uniform(2.4, 2.55, 500)])
+    elif name == "AERO_RA":        # is_sm_et.hpp:116-140 (Uz, hc, Z_u, Z_e); the model calls it with Z = 1.3333 hc
+        rows = [[uz, hc, hc * k, hc * k] for uz, hc, k in itertools.product(
+            [0.001, 0.5, 2.0, 30.0], [0.0, 1e-3, 0.06, 0.5, 2.0, 25.0], [0.67, 1.0, 1.3333, 4.0])]
+        rows += [[2.0, 0.5, 10.0, 2.0], [2.0, 12.0, 10.0, 2.0], [0.0, 0.5, 2.0, 2.0]]   # |Z - d| with Z < d; Uz = 0
+        rnd = np.column_stack([rng.uniform(0.001, 20, 500), rng.uniform(0.01, 20, 500), rng.uniform(0.5, 40, 500),
+                               rng.uniform(0.5, 40, 500)])
     else:                          # River.hpp:115-127 via updateRiver (w0, bankslope, length, y)
         rows = list(itertools.product([0.0, 2.0, 25.0], [0.0, 1e-8, 0.5, 3.0], [100.0, 2500.0],
                                       [-1.0, -1e-9, 0.0, 1e-9, 0.7, 6.0]))
         rnd = np.column_stack([rng.uniform(0, 30, 500), rng.uniform(0, 3, 500), rng.uniform(50, 5000, 500),
                                rng.uniform(-0.5, 8, 500)])
     x = np.vstack([np.asarray(rows, dtype=np.float64), rnd])
-    assert x.shape[1] == NIN[KAT[name]]
+    assert x.shape[1] == (ET_NIN[name] if name in ET_KAT else NIN[KAT[name]])
     return np.ascontiguousarray(x)

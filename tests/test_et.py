@@ -63,3 +63,103 @@ def test_oracle_et_exits(what):
     o, py = oracle.OracleEt(etm), PyEt(etm)
     assert o.step(f) == (10, first_veg)
     assert py.step(f) == (10, first_veg)
+
+
+# ---- the prelude pinned to the reference's own updateAllTimeSeries / updateforcing / ET ---------------------------
+def _ref_prelude_check(rec, stride, tmp_path):
+    """the project's own forcing path (the C++ host readers' rows, shud_project_forcing) into OracleEt over ccw
+    with the cryosphere on, against what the reference dumped per ET step: bit for bit"""
+    import refio
+    from shud_rhs import host
+    indir = refio.unpack_et(tmp_path)
+    P = host.Project(indir, "ccw", cwd=str(tmp_path))
+    c = P.control()
+    assert c["cryosphere"] == 1 and c["et_step"] == 330.0
+    etm = P.et_model()
+    assert (etm.params["ft_surf_day"], etm.params["ft_sub_day"]) == (2, 3)
+    assert np.array_equal(P.array("y_is"), rec["ic_is"]) and np.array_equal(P.array("y_snow"), rec["ic_snow"])
+    oe = oracle.OracleEt(etm)
+    oe.set_state(P.array("y_is"), P.array("y_snow"))
+    names = dict(fu_surf="fu_surf", fu_sub="fu_sub")
+    partial = 0
+    for k in range(refio.ET_STEPS):
+        t = float(rec["t"][k])
+        assert t == c["start_time"] + k * c["et_step"]
+        assert oe.step(P.forcing(t, t + c["et_step"])) == (0, -1)
+        got = oe.get()
+        for key in refio.ET_KEYS + ["t_temp", "t_prcp", "rn_factor"]:
+            a, b = got[names.get(key, key)][::stride], rec[key][k]
+            assert _bitwise(a, b), f"ET step {k} {key}: {int((a != b).sum())} of {a.size} entries differ"
+        partial += int(((rec["fu_surf"][k] > 0) & (rec["fu_surf"][k] < 1)).sum())
+    assert partial > 0 and rec["qEleNetPrep"].max() > 0 and rec["qEleE_IC"].max() > 0     # the run is not trivial
+    assert np.unique(rec["fu_sub"][-1]).size > 1 or np.unique(rec["fu_sub"]).size > 2
+
+
+def test_oracle_et_vs_recorded_reference(tmp_path):
+    import sys
+    from conftest import ORACLE_DIR
+    sys.path.insert(0, f"{ORACLE_DIR}/ref")
+    import refio
+    _ref_prelude_check(refio.load_recording("ccw_et_prelude"), refio.ET_STRIDE, tmp_path)
+
+
+def test_oracle_et_vs_live_reference(tmp_path):
+    """a fresh run of the reference binary, every element; the committed recording must equal it.  Passes
+    vacuously (not skipped) where oracle/_ref/ was not built: the recorded test carries the comparison."""
+    import sys
+    from conftest import ORACLE_DIR
+    sys.path.insert(0, f"{ORACLE_DIR}/ref")
+    import refio
+    if not refio.live_status("ccw_et_prelude"):
+        return
+    ref_dir = tmp_path / "ref"
+    live = refio.run_et_case(ref_dir, stride=1)
+    _ref_prelude_check(live, 1, tmp_path / "own")
+    rec = refio.load_recording("ccw_et_prelude")
+    for key, v in rec.items():
+        w = live[key][:, ::refio.ET_STRIDE] if live[key].ndim == 2 else live[key]
+        assert _bitwise(v, w), f"recording ccw_et_prelude: {key} is stale"
+
+
+# ---- the long sequence: full day-mean queues, exact thresholds (tests/et_long.py) --------------------------------
+@pytest.mark.parametrize("n", [1, 63, 257, 1031])
+def test_long_sequence_oracle_vs_python(n):
+    import et_long
+    etm, y_is, y_snow = et_long.et_model(n)
+    o, py = oracle.OracleEt(etm), PyEt(etm)
+    o.set_state(y_is, y_snow)
+    py.y_is[:], py.y_snow[:] = y_is, y_snow
+    hit = dict(snow_lo=0, snow_hi=0, melt0=0, cap=0, meltlim=0)
+    for k, f in enumerate(et_long.forcings()):
+        ic_before, sn_before = py.y_is.copy(), py.y_snow.copy()
+        assert o.step(f) == (0, -1)
+        assert py.step(f) == (0, -1)
+        got = o.get()
+        for key in KEYS:
+            assert _bitwise(got[key], py.out[key]), f"step {k} {key}"
+        T = py.out["t_temp"]
+        na = (etm.arrays["iforc"] == 3) | (etm.arrays["z_surf"] == -9999.0)
+        assert np.array_equal(T[na], f.station[etm.arrays["iforc"][na], 2])          # temp == t0 exactly
+        hit["snow_lo"] += int((T == -3.0).sum())
+        hit["snow_hi"] += int((T == 1.0).sum())
+        hit["melt0"] += int((T == 0.0).sum())
+        vg = etm.arrays["veg_frac"]
+        lai = py.out["t_lai"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            hit["cap"] += int(((vg > 1e-10) & (lai > 1e-10) & (ic_before / vg > 0.0002 * lai)).sum())
+        dt = f.t_next - f.t
+        hit["meltlim"] += int(((sn_before > 0) & (T > 0) & (T * py.out["t_mf"] > sn_before / dt)).sum())
+        if k == 0 or k == 9 or k == 10:      # CACHED before any RECOMPUTE; all-night RECOMPUTE and its CACHED step
+            assert np.all(py.out["rn_factor"] == 0.0)
+        if k == 1:
+            assert np.any(py.out["rn_factor"] > 0.0)
+    # every element's queues: seven pushes, the 2-day queue popped five times and the 3-day queue four times,
+    # day means over a varying number of samples
+    for acc, days in ((py.acc_s, 2), (py.acc_g, 3)):
+        for a in acc:
+            assert a.pushes == 7 >= 3 + 3 and a.pops == 7 - days and len(a.q) == days
+            assert len(set(a.n_of_day[1:])) > 1
+    if n >= 63:
+        assert all(v > 0 for v in hit.values()), hit
+    fu = py.out["fu_surf"]
+    assert n < 63 or ((fu > 0) & (fu < 1)).any()

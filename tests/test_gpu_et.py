@@ -93,3 +93,86 @@ def test_device_et_exits(what, bit, slot):
     e = ei.value.err
     assert e["exit_code"] == 10 and e["flags"] & bit and e["first_index"][slot] == idx, e
     h.close()
+
+
+# ---- the long sequence: full day-mean queues (pop branch, ring wrap-around), exact thresholds ---------------------
+def _sized_model(n):
+    """a handle-able mesh of n elements (1, 63, 257) or a synthetic one of a few thousand"""
+    if n == 1:
+        return cases.single_element()[0]
+    m0, _ = cases.ccw()
+    if n <= m0.num_ele:
+        return cases._subset(m0, np.arange(n))
+    return cases.variant(n, seed=17)[0]
+
+
+@pytest.mark.parametrize("n", [1, 63, 257, 4000])
+def test_device_et_long_sequence(n, layout):
+    """tests/et_long.py on the device against OracleEt (which tests/test_et.py holds to PyEt bit for bit, with the
+    queue pushes and pops counted there): 28 steps, 7 day pushes, the 2-day queue pops 5 times and the 3-day queue
+    4 times with its ring wrapping, sizes below / across one and several 256-thread blocks.
+    t_*, rn_factor, yEleSnow, fu_surf, fu_sub use IEEE-exact operations only in the reference's order (the kernels
+    are built with -ffp-contract=off): bit-equal, so a wrong ring slot or a wrong day count cannot hide inside a
+    tolerance.  The outputs that pass through exp / log keep the parity tolerance."""
+    import et_long
+    from shud_rhs import runtime as rt
+    m = _sized_model(n)
+    ne = m.num_ele
+    assert ne == n or (n == 4000 and 3000 < ne < 5000 and ne % 256 != 0)
+    etm, y_is, y_snow = et_long.et_model(ne)
+    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
+    assert h.layout()["packed"] == (layout == "packed"), (n, h.layout())      # every size takes both layouts
+    h.set_step_inputs(step=workload.random_step_inputs(m, seed=3))
+    h.et_attach(etm)
+    h.et_set_state(y_is, y_snow)
+    oe = oracle.OracleEt(etm)
+    oe.set_state(y_is, y_snow)
+    fs = et_long.forcings(first_cached=False)
+    cached = et_long.forcings()[0]
+    with pytest.raises(rt.ShudRhsError) as ei:            # the handle refuses CACHED before any RECOMPUTE ...
+        h.et_step(cached)
+    assert ei.value.code == abi.SHUD_ERR_ARG              # ... before it touches its day-mean bookkeeping
+    for k, f in enumerate(fs):
+        assert h.et_step(f) == abi.SHUD_OK
+        assert oe.step(f) == (0, -1)
+        got, ref = h.et_get(), oe.get()
+        for key in KEYS:
+            if key in et_long.EXACT:
+                same = (got[key] == ref[key]) | (np.isnan(got[key]) & np.isnan(ref[key]))
+                assert same.all(), f"step {k} {key}: {(~same).sum()} of {ne} differ, first {np.argmax(~same)}"
+            else:
+                assert_close(got[key], ref[key], what=f"step {k} {key}")
+    assert ((ref["fu_surf"] > 0) & (ref["fu_surf"] < 1)).any() or n == 1
+    h.close()
+
+
+def test_device_et_vs_recorded_reference(tmp_path, layout):
+    """shud_et_step over ccw with the cryosphere on and short queues, fed by the C++ host's forcing rows, against
+    what the reference's own updateforcing / ET dumped per step (tests/golden/ref/ccw_et_prelude: every third
+    element, 22 steps of 330 min, both queues pop): the ET parity tolerance."""
+    import sys
+    from conftest import ORACLE_DIR, load_fixture
+    sys.path.insert(0, f"{ORACLE_DIR}/ref")
+    import refio
+    from shud_rhs import host
+    from shud_rhs import runtime as rt
+    rec = refio.load_recording("ccw_et_prelude")
+    indir = refio.unpack_et(tmp_path)
+    P = host.Project(indir, "ccw", cwd=str(tmp_path))
+    c = P.control()
+    m, _ = load_fixture("ccw")
+    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
+    assert h.layout()["packed"] == (layout == "packed")
+    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
+    h.et_attach(P.et_model())
+    h.et_set_state(P.array("y_is"), P.array("y_snow"))
+    worst = {}
+    for k in range(refio.ET_STEPS):
+        t = float(rec["t"][k])
+        assert h.et_step(P.forcing(t, t + c["et_step"])) == abi.SHUD_OK
+        got = h.et_get()
+        for key in refio.ET_KEYS + ["t_temp", "t_prcp", "rn_factor"]:
+            a, r = assert_close(got[key][::refio.ET_STRIDE], rec[key][k], what=f"ET step {k} {key}")
+            worst[key] = max(worst.get(key, 0.0), r)
+    print("REFPIN ccw_et_prelude", layout, {k: f"{v:.2e}" for k, v in worst.items()})
+    h.close()

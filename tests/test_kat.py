@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ATOL, ORACLE_DIR, PKG_DIR, RTOL
-from kat_grids import KAT, grid
+from kat_grids import ET_KAT, KAT, grid
 
 ZERO, EPSILON, EPS_SLOPE, PI, GRAV = 1e-10, 0.005, 0.05e-6, 3.1415926, 9.8
 _LIBM = C.CDLL("libm.so.6")                 # glibc cbrt (Python 3.10's math has none; numpy's is not glibc)
@@ -31,6 +31,11 @@ def _oracle_lib():
 
 def oracle_kat(name, x):
     out = np.zeros(x.shape[0])
+    if name in ET_KAT:                      # the ET leaves live in shud_oracle_et.c
+        lib = _oracle_lib()
+        lib.oracle_et_kat.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        assert lib.oracle_et_kat(ET_KAT[name], x.ctypes.data, x.shape[0], out.ctypes.data) == 0
+        return out
     assert _oracle_lib().oracle_kat(KAT[name], x.ctypes.data, x.shape[0], out.ctypes.data) == 0
     return out
 
@@ -148,6 +153,43 @@ def test_oracle_leaf_kat_vs_python(name):
     got = oracle_kat(name, x)
     want = np.array([PY[name](*row) for row in x])
     bad = ~_same(got, want) | (np.signbit(got) != np.signbit(want))
+    assert not bad.any(), f"{name}: {bad.sum()} of {x.shape[0]} differ, first row {x[np.argmax(bad)]}"
+
+
+_REF_KAT = {}
+
+
+def _ref_kat_all():
+    """the reference's own leaf functions over every grid: live (libshud_ref_kat.so in a child process, which
+    must then equal the committed recording) where the library was built, the recording alone otherwise"""
+    if not _REF_KAT:
+        import sys
+        sys.path.insert(0, os.path.join(ORACLE_DIR, "ref"))
+        import refio
+        rec = refio.load_recording("kat")
+        _REF_KAT["rec"] = rec
+        _REF_KAT["live"] = None
+        if refio.live_status("leaf equations (ref_kat)"):
+            ids = {**KAT, **ET_KAT}
+            _REF_KAT["live"] = refio.ref_kat_child({n: (ids[n], grid(n)) for n in ids})
+    return _REF_KAT
+
+
+@pytest.mark.parametrize("name", list(KAT) + list(ET_KAT))
+def test_oracle_leaf_kat_vs_reference(name):
+    """oracle_kat against the reference model's own functions (ref_kat), bit for bit, NaN patterns and the sign
+    of zero included.  The ET leaves PET_PM_openwater, PET_Penman_Monteith and AerodynamicResistance have no
+    other known-answer test."""
+    r = _ref_kat_all()
+    x = grid(name)
+    got = oracle_kat(name, x)
+    want = r["rec"][name]
+    if r["live"] is not None:
+        live = r["live"][name]
+        assert live.shape == want.shape and np.array_equal(live.view(np.uint64), want.view(np.uint64)), \
+            f"{name}: the committed recording is stale (oracle/ref/record.py)"
+    assert want.shape == got.shape
+    bad = ~_same(got, want) | (~np.isnan(want) & (np.signbit(got) != np.signbit(want)))
     assert not bad.any(), f"{name}: {bad.sum()} of {x.shape[0]} differ, first row {x[np.argmax(bad)]}"
 
 

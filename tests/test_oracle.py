@@ -1,5 +1,5 @@
-"""CPU: the oracle itself (no GPU).  Since the reference RHS cannot be compiled here and ships no golden
-vectors ("parity unpinned"), the C restatement is pinned by (1) an independent numpy restatement that
+"""CPU: the oracle itself (no GPU).  Beside the comparison with the reference's own f() (tests/test_ref_pin.py),
+which covers the reference's projects, the C restatement is pinned on every other mesh by (1) an independent numpy restatement that
 must agree bit for bit, (2) identities the reference's algorithm guarantees (antisymmetric lateral
 fluxes, conservative segment/junction exchange, statefulness pattern), (3) reference error exits."""
 import numpy as np
