@@ -25,6 +25,7 @@ extern "C" {
 #define SHUD_ORDER_IDENTITY 0
 #define SHUD_ORDER_USER     1   /* user_perm[NE], validated as a permutation (SHUD_ERR_ARG otherwise)       */
 #define SHUD_ORDER_BFS      2   /* breadth-first over nabr (below)                                          */
+#define SHUD_ORDER_TILES    3   /* breadth-first pockets that each stop at a sharing-tile border (below)    */
 
 /* shud_rhs_permute: direction and shape */
 #define SHUD_PERM_TO_INTERNAL 0 /* dst[k] = src[perm[k]]                                                    */
@@ -36,7 +37,27 @@ extern "C" {
 /* ---- device-free (libshud_rhs.so, beside the table builder) ---- */
 /* perm[NE]: new element k is old perm[k].  SHUD_ORDER_BFS: components start from the unvisited elements in
  * ascending (number of nabr >= 0 slots, index); the queue is FIFO; an element's unvisited neighbours are
- * enqueued in slot order 0, 1, 2 when first seen. */
+ * enqueued in slot order 0, 1, 2 when first seen.
+ * SHUD_ORDER_TILES: the same search, cut into pockets that never cross a border of the T-element sharing tile
+ * (T = 256, the tile of the in-tile edge sharing), so that neighbours stay inside one tile at any mesh size (a
+ * breadth-first front of an N-element mesh is ~sqrt(N) wide and outgrows the tile above ~65k elements):
+ *     starts = elements ascending by (number of nabr >= 0 slots, index)        as SHUD_ORDER_BFS
+ *     done[] = false; out = []; seeds = FIFO
+ *     while len(out) < NE:
+ *         s = the first not-done element popped from seeds; if seeds runs empty, the next not-done element of starts
+ *         cap = T - (len(out) mod T)                      room left in the tile being filled
+ *         done[s] = true; q = FIFO [s]; n = 1
+ *         while q not empty:
+ *             i = q.pop_front(); out.append(i)
+ *             for slot in 0, 1, 2:
+ *                 v = nabr[slot][i]
+ *                 if v >= 0 and not done[v]:
+ *                     if n < cap: done[v] = true; q.push_back(v); n += 1
+ *                     else:       seeds.push_back(v)      a seed for a later tile; skipped when popped if done by then
+ *     perm = out
+ * A pocket that runs dry before cap leaves its tile to be filled from the next seed (that tile is then disconnected).
+ * Tiles are visited breadth-first over tiles (the seeds are FIFO).  The planner keeps seeds free of duplicates with a
+ * flag, which gives the same order (a later duplicate is always done when popped): memory is O(NE). */
 int shud_order_plan(const ShudMeshSoA *mesh, int kind, const int32_t *user_perm, int32_t *perm);
 
 /* The model under perm, in library-owned storage: every [NE] array gathered, every [3*NE] edge-major array

@@ -135,7 +135,13 @@ struct shud_rhs {
         int rc = dalloc(p, n);
         if (rc) return rc;
         if (n && src) HIP_TRY(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-        else if (n) HIP_TRY(hipMemset(*p, 0, n * sizeof(T)));
+        else if (n) {
+            // hipMemset of device memory does not wait for the fill, and the handle's stream is non-blocking, so
+            // nothing else orders the fill before that stream's next kernel: a diagnostic array was seen zeroed
+            // AFTER the replay kernel had written it (shud_ensure_diag, then launch_all at once).  Wait here.
+            HIP_TRY(hipMemset(*p, 0, n * sizeof(T)));
+            HIP_TRY(hipStreamSynchronize(nullptr));
+        }
         return 0;
     }
     template <class T>

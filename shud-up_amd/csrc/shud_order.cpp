@@ -1,6 +1,7 @@
 // shud_order.cpp — element locality ordering without a device (include/shud_order.h): the planner, the appliers
 // that carry a model into the planned numbering, and the host gather for any other per-element array.
 #include "shud_order.h"
+#include "shud_dev.h"                              // kShareTile: the tile SHUD_ORDER_TILES fills is share_plan's
 
 #include <algorithm>
 #include <cstring>
@@ -52,7 +53,8 @@ extern "C" int shud_order_plan(const ShudMeshSoA *m, int kind, const int32_t *us
         std::copy(user_perm, user_perm + NE, perm);
         return SHUD_OK;
     }
-    if (kind != SHUD_ORDER_BFS) return shud_fail(SHUD_ERR_ARG, "unknown order kind %d", kind);
+    if (kind != SHUD_ORDER_BFS && kind != SHUD_ORDER_TILES)
+        return shud_fail(SHUD_ERR_ARG, "unknown order kind %d", kind);
     if (!m->nabr) return shud_fail(SHUD_ERR_ARG, "null nabr");
     int rc = check_nabr(m);
     if (rc) return rc;
@@ -72,6 +74,41 @@ extern "C" int shud_order_plan(const ShudMeshSoA *m, int kind, const int32_t *us
     }
     std::vector<char> seen((size_t)std::max(NE, 1), 0);
     int head = 0, tail = 0;                        // perm itself is the FIFO: [head, tail) is queued
+    if (kind == SHUD_ORDER_TILES) {
+        // pockets of the same search, each capped at the room left in the sharing tile it starts in; a neighbour
+        // met at the cap seeds a later pocket.  seen: 1 = placed, 2 = waiting in seeds (at most once, so NE slots)
+        std::vector<int32_t> seeds((size_t)NE);
+        int sh = 0, st = 0, si = 0;
+        while (tail < NE) {
+            int r = -1;
+            while (sh < st && r < 0) {
+                const int v = seeds[sh++];
+                if (seen[v] != 1) r = v;
+            }
+            while (r < 0) {
+                const int v = starts[si++];
+                if (seen[v] != 1) r = v;
+            }
+            const int end = tail + (shud::kShareTile - tail % shud::kShareTile);   // one past the pocket's last slot
+            seen[r] = 1;
+            perm[tail++] = r;
+            while (head < tail) {
+                const int i = perm[head++];
+                for (int j = 0; j < 3; j++) {
+                    const int v = m->nabr[(size_t)j * NE + i];
+                    if (v < 0 || seen[v] == 1) continue;
+                    if (tail < end) {
+                        seen[v] = 1;
+                        perm[tail++] = v;
+                    } else if (!seen[v]) {
+                        seen[v] = 2;
+                        seeds[st++] = v;
+                    }
+                }
+            }
+        }
+        return SHUD_OK;
+    }
     for (int s = 0; s < NE; s++) {
         const int r = starts[s];
         if (seen[r]) continue;

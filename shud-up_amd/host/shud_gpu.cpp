@@ -1,7 +1,7 @@
 // shud_gpu.cpp — C++ host of the device path: SHUD() (src/Model/shud.cpp:32-170) with the RHS, the ET-step
 // prelude, the integrator and the outputs on one MI355X, driven through the C-ABIs of include/.
 //
-//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] [--reorder bfs]
+//   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] [--reorder bfs|tiles]
 //            <input_dir> <project>
 //   shud_gpu --rhs-check K | --rhs-bench [--evals N] ...   partitioned RHS modes (shud_gpu_part.cpp)
 //
@@ -35,7 +35,8 @@
 // shud_rhs_summary has already put boundary heads into the device arrays, which the reference's arrays do not hold
 // at that point.  --flood: FloodWarning(t) after ExportResults (shud.cpp:154) on the arrays summary and the
 // diagnostics replay have just filled, into <prj>.flood.csv.
-// --reorder bfs runs the whole device side in the breadth-first element order of include/shud_order.h: the mesh, the
+// --reorder bfs | tiles runs the whole device side in a planned element order of include/shud_order.h (bfs: breadth-
+// first; tiles: breadth-first pockets that stop at the borders of the 256-element sharing tile): the mesh, the
 // parameters, the ET mesh and the initial state (y, IS, snow) are carried into it by the appliers and the handles are
 // plain ones (the device ET prelude writes the step inputs straight into the handle, so the device side shares one
 // numbering).  Every file stays in the input's numbering: element outputs are registered with shud_out_add_mapped,
@@ -69,14 +70,16 @@ static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 
 static void usage() {
     fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots]\n"
-                    "                [--reorder bfs] <input_dir> <project>\n"
+                    "                [--reorder bfs|tiles] <input_dir> <project>\n"
                     "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n"
                     "  --flood         write <outdir>/<project>.flood.csv (reaches above their bank after each solver step)\n"
                     "  --ic-snapshots  write <outdir>/<project>.cfg.ic.bak and, every Update_IC_STEP minutes and at the\n"
                     "                  end, <outdir>/<project>.cfg.ic.update (restart file for INIT_MODE 3)\n"
                     "  Both are off by default (the reference always writes these files).\n"
-                    "  --reorder bfs   run the device side in a breadth-first element order (neighbours close in memory);\n"
-                    "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n");
+                    "  --reorder ORDER run the device side in a planned element order (neighbours close in memory);\n"
+                    "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n"
+                    "                  tiles: breadth-first pockets that each fill one 256-element sharing tile;\n"
+                    "                  the faster one at every mesh size measured (prefer it).  bfs: plain breadth-first.\n");
 }
 
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
@@ -146,8 +149,8 @@ int main(int argc, char **argv) {
     if (pos.size() != 2) { usage(); return 1; }
     const char *indir = pos[0], *prj = pos[1];
     if (outdir.empty()) outdir = std::string("output/") + prj + ".out";
-    if (!reorder.empty() && reorder != "bfs") {
-        fprintf(stderr, "--reorder: unknown order '%s' (bfs)\n", reorder.c_str());
+    if (!reorder.empty() && reorder != "bfs" && reorder != "tiles") {
+        fprintf(stderr, "--reorder: unknown order '%s' (bfs, tiles)\n", reorder.c_str());
         return 1;
     }
     if (!reorder.empty() && env_truthy(getenv("SHUD_WB_DIAG"))) {
@@ -206,7 +209,7 @@ int main(int argc, char **argv) {
         inv.resize((size_t)ne);
         ShudMeshSoA pm;
         ShudParamsSoA pp;
-        if (shud_order_plan(&mesh, SHUD_ORDER_BFS, nullptr, perm.data()) ||
+        if (shud_order_plan(&mesh, reorder == "tiles" ? SHUD_ORDER_TILES : SHUD_ORDER_BFS, nullptr, perm.data()) ||
             shud_order_apply(&mesh, &par, perm.data(), &ordered, &pm, &pp)) {
             fprintf(stderr, "--reorder: %s\n", shud_rhs_last_error_string());
             return 1;

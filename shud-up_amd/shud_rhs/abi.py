@@ -325,7 +325,7 @@ MON_FUNCTIONS = {
 
 
 # ---- include/shud_order.h (element locality ordering) ----
-SHUD_ORDER_IDENTITY, SHUD_ORDER_USER, SHUD_ORDER_BFS = 0, 1, 2
+SHUD_ORDER_IDENTITY, SHUD_ORDER_USER, SHUD_ORDER_BFS, SHUD_ORDER_TILES = 0, 1, 2, 3
 SHUD_PERM_TO_INTERNAL, SHUD_PERM_TO_CALLER = 0, 1
 SHUD_PERM_STATE, SHUD_PERM_ELE, SHUD_PERM_ELE3 = 0, 1, 2
 ORDER_FUNCTIONS = {

@@ -41,7 +41,7 @@ def _check(rc, what):
 class RhsHandle:
     def __init__(self, model, mode=abi.SHUD_MODE_SERIAL, device=0, stream=None, check_errors=True,
                  partition=None, order=None):
-        """order (include/shud_order.h): None = a plain handle; "identity", "bfs" or a permutation array (new
+        """order (include/shud_order.h): None = a plain handle; "identity", "bfs", "tiles" or a permutation array (new
         element k is old order[k]) = shud_rhs_create_ordered.  Host arrays stay in the model's numbering, device
         pointers are in the internal one (permute())."""
         self.model = model
@@ -280,10 +280,12 @@ class RhsHandle:
 
 
 def order_kind(order, num_ele):
-    """(SHUD_ORDER_*, user permutation or None) of an order= argument: "identity", "bfs" or a permutation array"""
+    """(SHUD_ORDER_*, user permutation or None) of an order= argument: "identity", "bfs", "tiles" or a permutation
+    array"""
     if isinstance(order, str):
         try:
-            return {"identity": abi.SHUD_ORDER_IDENTITY, "bfs": abi.SHUD_ORDER_BFS}[order], None
+            return {"identity": abi.SHUD_ORDER_IDENTITY, "bfs": abi.SHUD_ORDER_BFS,
+                    "tiles": abi.SHUD_ORDER_TILES}[order], None
         except KeyError:
             raise ValueError(f"unknown order {order!r}") from None
     up = np.ascontiguousarray(order, dtype=np.int32)
