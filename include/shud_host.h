@@ -82,6 +82,25 @@ int shud_project_wb_interval(shud_project_t p);
 /* CS.UpdateICStep [min]: Update_IC_STEP of <prj>.cfg.para (Model_Control.cpp:189; default 1440,
  * Model_Control.hpp:181), the schedule of the .cfg.ic.update snapshots (include/shud_mon.h); -1 for NULL */
 int shud_project_update_ic_step(shud_project_t p);
+/* OUTPUT_MODE and NCOUTPUT_CFG of <prj>.cfg.para (Model_Control.cpp:229-266: LEGACY / NETCDF / BOTH or 0 / 1 / 2; an
+ * invalid value fails the load, a key without a value is LEGACY with the reference's warning) with the checks of
+ * :591-634 (NETCDF / BOTH without NCOUTPUT_CFG, or with an unreadable one, fail the load; a relative path resolves
+ * against the .cfg.para's directory), and the KEY VALUE ncoutput cfg (NetcdfOutputContext.cpp:1093-1153): OUT_DIR,
+ * CRS_WKT (a file, read as text), SCHEMA (ignored with the reference's warning).  Relative values of that cfg resolve
+ * against the run directory: the parent of the parent of the cfg's directory. */
+typedef struct {
+    int32_t output_mode;                 /* 0 LEGACY (.dat / .csv), 1 NETCDF, 2 BOTH                             */
+    const char *ncoutput_cfg;            /* resolved path of the ncoutput cfg; "" in LEGACY mode                 */
+    const char *out_dir;                 /* OUT_DIR, resolved; "" = beside the legacy files                      */
+    const char *crs_wkt;                 /* text of the CRS_WKT file; "" = none                                  */
+    const char *schema;                  /* SCHEMA, resolved (not used); "" = none                               */
+    const char *warnings;                /* the reference's warnings for these keys (also on stderr), '\n'-ended */
+} ShudNcOutputCfg;
+int shud_project_ncoutput(shud_project_t p, ShudNcOutputCfg *c);
+/* the mesh as <prj>.ele.nc describes it: node x (which = 0) / y (1) by node index, n = NumNode; the element node
+ * indices [NumEle][3], 1-based as in <prj>.sp.mesh, n = NumEle (centroids: shud_project_array "x" / "y") */
+const double *shud_project_node_xy(shud_project_t p, int which, int64_t *n);
+const int32_t *shud_project_ele_nodes(shud_project_t p, int64_t *n);
 /* Riv[i].type of <prj>.sp.riv, 1-based as in the file (the Type column of <prj>.flood.csv); n = NumRiv */
 const int32_t *shud_project_riv_type(shud_project_t p, int64_t *n);
 

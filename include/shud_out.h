@@ -11,13 +11,19 @@
  *   Print_Ctrl::fun_printBINARY/ASCII   src/classes/Model_Control.cpp:893-909
  * Each exported step adds every registered variable into its device-resident buffer with one batched
  * kernel (no PCIe traffic); only at the end of an output interval is the buffer scaled on the device,
- * copied to the host and written, in the reference's byte layout.  NetCDF sinks are out of scope.
+ * copied to the host and written, in the reference's byte layout.
+ *
+ * NetCDF sinks (OUTPUT_MODE NETCDF / BOTH; MD_initialize.cpp:346-371, NetcdfOutputContext.cpp:953-1085): up to three
+ * files of include/shud_nc.h are attached to an output set and a control is registered with a sink in one of them,
+ * alone or beside its .dat / .csv.  At the interval's end the control's record slab is formed on the device (the
+ * float of the same mean, big-endian, fill at unselected columns) and crosses PCIe at 4 bytes per value.
  */
 #ifndef SHUD_OUT_H
 #define SHUD_OUT_H
 
 #include <stdint.h>
 
+#include "shud_nc.h"
 #include "shud_rhs.h"
 
 #ifdef __cplusplus
@@ -107,6 +113,22 @@ int shud_out_add(shud_out_t o, const ShudPrintSpec *spec);
  * d_src[col_src[c]], col_src host [n_all] with values in [0, n_all); flag_io and the header's column numbers are
  * still indexed by the caller's column c.  A create-time change: the export kernel already reads index lists. */
 int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *spec, const int32_t *col_src);
+/* attaches the NetCDF file spec->kind describes (one per kind) to the output set; controls are then registered into
+ * it with shud_out_add_nc.  Nothing is written yet; an OUT_DIR that exists and is no directory is refused here. */
+int shud_out_attach_nc(shud_out_t o, const ShudNcSpec *spec);
+/* shud_out_add / shud_out_add_mapped (col_src NULL / non-NULL) with a NetCDF sink in the attached file `kind`
+ * (setSink, MD_initialize.cpp:348-356): the variable is named after the leaf of spec->basename past its last dot.
+ * legacy != 0 (OUTPUT_MODE BOTH): the .dat / .csv of spec->binary / ascii are written too, from the same product;
+ * legacy == 0 (NETCDF): neither is opened and no double snapshot is copied (MD_initialize.cpp:362-363).
+ * A NetCDF header cannot grow after its first record: refused once the headers are final (shud_out_nc_begin). */
+int shud_out_add_nc(shud_out_t o, const ShudPrintSpec *spec, const int32_t *col_src, int32_t kind, int32_t legacy);
+/* writes the header and the fixed variables of every attached file that has a control; implied by the first
+ * shud_out_export.  A file that never gets a record stays valid, with 0 records. */
+int shud_out_nc_begin(shud_out_t o);
+/* measurement only (tools/nc_bench.py): device time [ms] of one launch of control k's interval-end kernel (the mean,
+ * the float slab, the snapshot in BOTH mode, the zeroing), averaged over `reps` back-to-back launches after a warm-up.
+ * It zeroes the control's accumulator. */
+int shud_out_time_nc(shud_out_t o, int k, int reps, double *ms_pass);
 /* Control_Data::ExportResults(t): every control adds its source into its buffer; controls whose interval
  * ends at t (floor(t + 0.001) % Interval == 0) write the interval mean and reset.  Sources must hold the
  * values to export (shud_rhs_summary / shud_rhs_refresh_diagnostics first), stream-ordered.  The rows of a

@@ -14,7 +14,17 @@
 // append the rows once that copy's event has fired.  The time loop only waits when both banks are still being
 // written (the reference writes synchronously inside ExportResults; the bytes written are the same, in the
 // same order).
+//
+// NetCDF sinks (OUTPUT_MODE NETCDF / BOTH, include/shud_nc.h): a control registered with shud_out_add_nc keeps, beside
+// its accumulator, the on-disk record slab of its variable on the device: n_all big-endian float words, fill at every
+// unselected position (written once at registration).  At the interval's end one kernel forms k_snap's product, stores
+// its float (round-to-nearest-even, bytes swapped) at the selected positions of the slab, the double into the
+// snapshot when a .dat / .csv is written too, and zeroes the accumulator.  The slab crosses PCIe at 4 bytes per
+// value into pinned banks of its own and the control's writer thread places it with one positioned write; the record
+// index is fixed by the exporting thread (control order, as the reference's ensureTimeIndex sees it).
 #include <hip/hip_runtime.h>
+
+#include <sys/stat.h>
 
 #include <cmath>
 #include <condition_variable>
@@ -27,7 +37,9 @@
 
 #include "shud_diag_host.h"
 #include "shud_handle.h"
+#include "shud_nc.h"
 #include "shud_out.h"
+#include "shud_reduce.h"
 
 namespace {
 
@@ -51,6 +63,57 @@ __global__ void __launch_bounds__(256) k_snap(double *__restrict__ buf, double *
         snap[i] = buf[i] * f;
         buf[i] = 0.0;
     }
+}
+
+// The interval's end of a control with a NetCDF sink.  mean = buf[j] * f is k_snap's product; slab position p holds the
+// big-endian bits of (float)mean of its column j (out[idx0] = (float)buffer[j], NetcdfOutputContext.cpp:1000), or the
+// fill; snap (BOTH mode; else nullptr) receives the same double; buf is zeroed once.  A lane owns four consecutive slab
+// positions and writes them with one 16-byte store (slab, buf, snap and col are allocated in whole quads, so there is
+// no tail); the slab and the snapshot are single-use streams on their way to the host: non-temporal stores where a
+// lane writes 16 bytes.
+__device__ __forceinline__ uint32_t be_float(double m) { return __builtin_bswap32(__float_as_uint((float)m)); }
+
+// every column selected: position p is column p
+__global__ void __launch_bounds__(256) k_snap_nc(double *__restrict__ buf, double *__restrict__ snap,
+                                                 uint32_t *__restrict__ slab, int nquad, double f) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nquad) return;
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    v2d *b = (v2d *)buf + 2 * (size_t)q;
+    const v2d a0 = b[0], a1 = b[1];
+    const v2d m0 = a0 * f, m1 = a1 * f;
+    b[0] = (v2d){0.0, 0.0};
+    b[1] = (v2d){0.0, 0.0};
+    if (snap) {
+        shud::red::stn((v2d *)snap + 2 * (size_t)q, m0);
+        shud::red::stn((v2d *)snap + 2 * (size_t)q + 1, m1);
+    }
+    shud::red::stn((v4u *)slab + q, (v4u){be_float(m0.x), be_float(m0.y), be_float(m1.x), be_float(m1.y)});
+}
+
+// a column selection: col[p] is the selected column at position p, -1 where the slab keeps its fill
+__global__ void __launch_bounds__(256) k_snap_nc_sel(double *__restrict__ buf, double *__restrict__ snap,
+                                                     uint32_t *__restrict__ slab, const int *__restrict__ col,
+                                                     int nquad, double f) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nquad) return;
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const v4i j4 = ((const v4i *)col)[q];
+    const int j[4] = {j4.x, j4.y, j4.z, j4.w};
+    uint32_t w[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        w[u] = __builtin_bswap32(SHUD_NC_FILL_BITS);
+        if (j[u] >= 0) {
+            const double m = buf[j[u]] * f;
+            buf[j[u]] = 0.0;
+            if (snap) snap[j[u]] = m;                            // 8-byte pieces: plain stores, merged in L2
+            w[u] = be_float(m);
+        }
+    }
+    shud::red::stn((v4u *)slab + q, (v4u){w[0], w[1], w[2], w[3]});
 }
 
 // Model_Data::summary (MD_update.cpp:190-216): element storages and river stage from a state vector, BC
@@ -93,11 +156,18 @@ struct PrintCtrl {
     double *h_buf[2] = {nullptr, nullptr};   // pinned banks for the interval mean
     FILE *fb = nullptr, *fa = nullptr;
     int64_t rows = 0;
+    // NetCDF sink (shud_out_add_nc): file kind (-1: none), the control's id in that file, the record slab on the
+    // device (whole quads), its pinned banks, and the position -> column list when a selection masks some columns
+    int nc_kind = -1, nc_ctrl = -1;
+    bool legacy = true;                  // a .dat / .csv is written too: the double snapshot is formed and copied
+    uint32_t *d_slab = nullptr, *h_slab[2] = {nullptr, nullptr};
+    int *d_col = nullptr;
 };
 
 struct OutTask {                         // one row of one control: (bank, control, left endpoint of the interval)
     int bank, ctrl;
     double tq;
+    int64_t rec;                         // NetCDF record of tq (fixed at export, in control order)
 };
 constexpr int kWriters = 4;
 
@@ -124,6 +194,8 @@ struct shud_out {
     // shud_out_rows / shud_out_destroy; rows whose copy failed are never written (no stale bank reaches a file)
     int werr = 0;
     std::string werr_msg;
+    shud_nc_t nc[SHUD_NC_KINDS] = {nullptr, nullptr, nullptr};   // attached NetCDF files
+    bool nc_begun = false;
 };
 static void writer_fail(shud_out *o, int code, const std::string &msg) {
     std::lock_guard<std::mutex> lk(o->mu);
@@ -158,6 +230,12 @@ static void writer_loop(shud_out *o, int w) {
                 const size_t w1 = fwrite(&job.tq, sizeof(double), 1, p.fb);
                 const size_t w2 = fwrite(hb, sizeof(double), p.numvar, p.fb);
                 if (w1 != 1 || w2 != (size_t)p.numvar) writer_fail(o, SHUD_ERR_ARG, "write error on " + p.filename + ".dat");
+            }
+            if (p.nc_ctrl >= 0) {                                    // Netcdf*VarSink::onWrite
+                shud_nc_t nc = o->nc[p.nc_kind];
+                int64_t rec = job.rec;
+                if (shud_nc_record(nc, job.tq, &rec) || shud_nc_put_slab(nc, p.nc_ctrl, rec, p.h_slab[job.bank]))
+                    writer_fail(o, SHUD_ERR_ARG, shud_nc_last_error());
             }
         }
         {
@@ -203,8 +281,12 @@ extern "C" int shud_out_create(int device, void *stream, shud_out_t *out) {
 
 // Print_Ctrl::Init / InitIJ (Model_Control.cpp:759-858) + open_file (:683-758)
 // col_src (NULL: identity): caller column c reads d_src[col_src[c]]; flag_io and the header's icol stay by caller column
-static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src) {
+// nc_kind >= 0: a NetCDF sink in the attached file of that kind; legacy = false: no .dat / .csv beside it
+static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src, int nc_kind = -1, bool legacy = true) {
     if (!o || !s || !s->basename || !s->d_src) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (nc_kind >= 0 && (nc_kind >= SHUD_NC_KINDS || !o->nc[nc_kind]))
+        return shud_fail(SHUD_ERR_ARG, "Print_Ctrl %s: no NetCDF file of kind %d attached (shud_out_attach_nc)",
+                         s->basename, nc_kind);
     if (col_src)
         for (int i = 0; i < s->n_all; i++)
             if (col_src[i] < 0 || col_src[i] >= s->n_all)
@@ -228,18 +310,43 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src)
     }
     p.numvar = (int)sel.size();
     if (p.numvar <= 0) fprintf(stderr, "WARNING: Empty columns in %s.\n;", p.filename.c_str());
-    const size_t nb = std::max(p.numvar, 1);
+    p.legacy = legacy;
+    if (nc_kind >= 0) {                                              // Netcdf*VarSink::onInit
+        std::vector<int32_t> icol(p.icol.begin(), p.icol.end());
+        int32_t ctrl = -1;
+        if (shud_nc_add_var(o->nc[nc_kind], s->basename, s->n_all, s->start_time, icol.data(), p.numvar, &ctrl))
+            return shud_fail(SHUD_ERR_ARG, "shud_out_add_nc: %s", shud_nc_last_error());
+        p.nc_kind = nc_kind;
+        p.nc_ctrl = ctrl;
+    }
+    const size_t nb = ((size_t)std::max(p.numvar, 1) + 3) / 4 * 4;   // whole quads (k_snap_nc)
     HIP_TRY(hipMalloc(&p.d_buf, nb * sizeof(double)));
-    HIP_TRY(hipMalloc(&p.d_snap, nb * sizeof(double)));
     HIP_TRY(hipMemsetAsync(p.d_buf, 0, nb * sizeof(double), o->stream));   // buffer[k] = 0.0
-    for (int b = 0; b < 2; b++) HIP_TRY(hipHostMalloc(&p.h_buf[b], nb * sizeof(double), hipHostMallocDefault));
+    if (legacy) {
+        HIP_TRY(hipMalloc(&p.d_snap, nb * sizeof(double)));
+        for (int b = 0; b < 2; b++) HIP_TRY(hipHostMalloc(&p.h_buf[b], nb * sizeof(double), hipHostMallocDefault));
+    }
+    if (nc_kind >= 0) {
+        // the slab as it goes to disk: fill everywhere; the selected positions are rewritten at every interval's end
+        const size_t nq = ((size_t)std::max(s->n_all, 1) + 3) / 4 * 4;
+        std::vector<uint32_t> fill(nq, __builtin_bswap32(SHUD_NC_FILL_BITS));
+        HIP_TRY(hipMalloc(&p.d_slab, nq * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(p.d_slab, fill.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        for (int b = 0; b < 2; b++) HIP_TRY(hipHostMalloc(&p.h_slab[b], nq * sizeof(uint32_t), hipHostMallocDefault));
+        if (p.numvar < s->n_all) {
+            std::vector<int> col(nq, -1);
+            for (int k = 0; k < p.numvar; k++) col[(size_t)p.icol[k] - 1] = k;
+            HIP_TRY(hipMalloc(&p.d_col, nq * sizeof(int)));
+            HIP_TRY(hipMemcpy(p.d_col, col.data(), nq * sizeof(int), hipMemcpyHostToDevice));
+        }
+    }
     if (col_src || (s->flag_io && p.numvar < s->n_all)) {
         HIP_TRY(hipMalloc(&p.d_sel, nb * sizeof(int)));
         HIP_TRY(hipMemcpy(p.d_sel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     // open_file: fixed 1024-byte header, StartTime, NumVar, icol (binary); the ASCII twin's preamble
     const char *mode = s->solar_lonlat_mode ? s->solar_lonlat_mode : "";
-    if (s->binary) {
+    if (legacy && s->binary) {
         const std::string fb = p.filename + ".dat";
         p.fb = fopen(fb.c_str(), "wb");
         if (!p.fb) return out_fail_io("shud_out_add", fb);
@@ -248,7 +355,7 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src)
                                        s->solar_lon_deg, s->solar_lat_deg, (double)p.start_time, p.numvar,
                                        p.icol.data());
     }
-    if (s->ascii) {
+    if (legacy && s->ascii) {
         const std::string fa = p.filename + ".csv";
         p.fa = fopen(fa.c_str(), "w");
         if (!p.fa) return out_fail_io("shud_out_add", fa);
@@ -283,11 +390,73 @@ extern "C" int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *s, const i
     return out_add(o, s, col_src);
 }
 
+// NetCDF sinks: NetcdfOutputContext's three files (NetcdfOutputContext.cpp:1155-1175) and setSink (MD_initialize.cpp:
+// 348-356)
+extern "C" int shud_out_attach_nc(shud_out_t o, const ShudNcSpec *spec) {
+    if (!o || !spec) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (spec->kind < 0 || spec->kind >= SHUD_NC_KINDS) return shud_fail(SHUD_ERR_ARG, "shud_out_attach_nc: unknown kind %d", spec->kind);
+    if (o->nc[spec->kind]) return shud_fail(SHUD_ERR_ARG, "shud_out_attach_nc: a file of kind %d is already attached", spec->kind);
+    // the output directory must be usable now, not at the first record: OUT_DIR that is a regular file, ...
+    if (spec->out_dir && spec->out_dir[0]) {
+        struct stat st;
+        if (stat(spec->out_dir, &st) == 0 && !S_ISDIR(st.st_mode))
+            return shud_fail(SHUD_ERR_ARG, "shud_out_attach_nc: OUT_DIR %s exists and is not a directory", spec->out_dir);
+    }
+    if (shud_nc_create(spec, &o->nc[spec->kind])) return shud_fail(SHUD_ERR_ARG, "shud_out_attach_nc: %s", shud_nc_last_error());
+    return SHUD_OK;
+}
+
+extern "C" int shud_out_add_nc(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src, int32_t kind, int32_t legacy) {
+    if (kind < 0) return shud_fail(SHUD_ERR_ARG, "shud_out_add_nc: kind %d", kind);
+    if (o && o->nc_begun) return shud_fail(SHUD_ERR_ARG, "shud_out_add_nc: the NetCDF headers are final (a control "
+                                           "with a NetCDF sink is registered before the first export)");
+    return out_add(o, s, col_src, kind, legacy != 0);
+}
+
+// the headers and fixed variables of every attached file that has a control (no later than the first export)
+extern "C" int shud_out_nc_begin(shud_out_t o) {
+    if (!o) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (o->nc_begun) return SHUD_OK;
+    for (int k = 0; k < SHUD_NC_KINDS; k++)
+        if (o->nc[k] && shud_nc_num_ctrl(o->nc[k]) > 0 && shud_nc_begin(o->nc[k]))
+            return shud_fail(SHUD_ERR_ARG, "shud_out_nc_begin: %s", shud_nc_last_error());
+    o->nc_begun = true;
+    return SHUD_OK;
+}
+
+static void launch_snap_nc(shud_out *o, PrintCtrl &p, double f) {
+    const int nquad = (p.numall + 3) / 4;
+    if (p.d_col)
+        hipLaunchKernelGGL(k_snap_nc_sel, dim3((nquad + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap,
+                           p.d_slab, p.d_col, nquad, f);
+    else
+        hipLaunchKernelGGL(k_snap_nc, dim3((nquad + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap, p.d_slab,
+                           nquad, f);
+}
+
+// measurement only: the interval-end kernel of control k, `reps` times back to back (it zeroes the accumulator)
+extern "C" int shud_out_time_nc(shud_out_t o, int k, int reps, double *ms_pass) {
+    if (!o || !ms_pass || reps < 1 || k < 0 || k >= (int)o->pc.size()) return shud_fail(SHUD_ERR_ARG, "bad argument");
+    PrintCtrl &p = o->pc[k];
+    if (p.nc_ctrl < 0 || p.numvar <= 0) return shud_fail(SHUD_ERR_ARG, "shud_out_time_nc: control %d has no NetCDF sink", k);
+    HIP_TRY(hipSetDevice(o->device));
+    if (out_drain(o)) return out_report(o);
+    return shud::time_passes(o->stream, reps, [&]() -> int {
+        launch_snap_nc(o, p, 1.0);
+        HIP_TRY(hipGetLastError());
+        return SHUD_OK;
+    }, ms_pass);
+}
+
 // Control_Data::ExportResults (Model_Control.cpp:123-127) -> Print_Ctrl::PrintData (:926-960) for every control
 extern "C" int shud_out_export(shud_out_t o, double t) {
     if (!o) return shud_fail(SHUD_ERR_ARG, "null argument");
     if (o->pc.empty()) return SHUD_OK;
     HIP_TRY(hipSetDevice(o->device));
+    if (!o->nc_begun) {
+        const int rc = shud_out_nc_begin(o);
+        if (rc) return rc;
+    }
     if (o->max_nvar > 0) {
         const int gx = std::min((o->max_nvar + 255) / 256, 2048);
         hipLaunchKernelGGL(k_accumulate, dim3(gx, (unsigned)o->pc.size()), dim3(256), 0, o->stream, o->d_slots);
@@ -301,7 +470,7 @@ extern "C" int shud_out_export(shud_out_t o, double t) {
         PrintCtrl &p = o->pc[k];
         p.num_update++;
         if (t_floor % p.interval != 0) continue;
-        rows.push_back(OutTask{bank, (int)k, (double)(t_floor - (long long)p.interval)});   // left endpoint
+        rows.push_back(OutTask{bank, (int)k, (double)(t_floor - (long long)p.interval), -1});   // left endpoint
     }
     if (rows.empty()) return SHUD_OK;
     // a free host bank (the writers may still be writing the one used two events ago)
@@ -314,26 +483,35 @@ extern "C" int shud_out_export(shud_out_t o, double t) {
     for (const auto &r : rows) {
         PrintCtrl &p = o->pc[r.ctrl];
         const double f = p.tau / p.num_update;
-        if (p.numvar > 0)
+        if (p.numvar <= 0) continue;
+        if (p.nc_ctrl < 0) {
             hipLaunchKernelGGL(k_snap, dim3((p.numvar + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap,
                                p.numvar, f);
+        } else {
+            launch_snap_nc(o, p, f);
+        }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(o->ev_snap, o->stream));
     HIP_TRY(hipStreamWaitEvent(o->s_copy, o->ev_snap, 0));
     for (const auto &r : rows) {
         PrintCtrl &p = o->pc[r.ctrl];
-        if (p.numvar > 0)
+        if (p.numvar > 0 && p.legacy)
             HIP_TRY(hipMemcpyAsync(p.h_buf[bank], p.d_snap, p.numvar * sizeof(double), hipMemcpyDeviceToHost,
+                                   o->s_copy));
+        if (p.nc_ctrl >= 0 && p.numall > 0)
+            HIP_TRY(hipMemcpyAsync(p.h_slab[bank], p.d_slab, (size_t)p.numall * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    o->s_copy));
     }
     HIP_TRY(hipEventRecord(o->ev_copied[bank], o->s_copy));
     // every launch and copy is enqueued: only now are the rows committed (a failure above returns with the
     // intervals still open and nothing queued for the writers)
-    for (const auto &r : rows) {
+    for (auto &r : rows) {
         PrintCtrl &p = o->pc[r.ctrl];
         p.num_update = 0;
         p.rows++;
+        // the record's index, in control order (ensureTimeIndex); a failure here surfaces from the writer's own call
+        if (p.nc_ctrl >= 0) (void)shud_nc_reserve(o->nc[p.nc_kind], r.tq, &r.rec);
     }
     o->bank ^= 1;
     o->copy_pending = true;
@@ -378,16 +556,23 @@ extern "C" int shud_out_destroy(shud_out_t o) {
         if (p.d_buf) (void)hipFree(p.d_buf);
         if (p.d_snap) (void)hipFree(p.d_snap);
         if (p.d_sel) (void)hipFree(p.d_sel);
-        for (int b = 0; b < 2; b++)
+        if (p.d_slab) (void)hipFree(p.d_slab);
+        if (p.d_col) (void)hipFree(p.d_col);
+        for (int b = 0; b < 2; b++) {
             if (p.h_buf[b]) (void)hipHostFree(p.h_buf[b]);
+            if (p.h_slab[b]) (void)hipHostFree(p.h_slab[b]);
+        }
     }
+    int nrc = SHUD_OK;
+    for (int k = 0; k < SHUD_NC_KINDS; k++)                  // a file with no record is still written, with 0 records
+        if (o->nc[k] && shud_nc_close(o->nc[k]) && !nrc) nrc = shud_fail(SHUD_ERR_ARG, "shud_out: %s", shud_nc_last_error());
     if (o->d_slots) (void)hipFree(o->d_slots);
     if (o->ev_snap) (void)hipEventDestroy(o->ev_snap);
     for (int b = 0; b < 2; b++)
         if (o->ev_copied[b]) (void)hipEventDestroy(o->ev_copied[b]);
     if (o->s_copy) (void)hipStreamDestroy(o->s_copy);
     delete o;
-    return rc;
+    return rc ? rc : nrc;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -43,8 +43,15 @@
 // restart snapshots with shud_mon_set_ic_order, .cfg.ic.bak comes from the input's own arrays; flood alerts are
 // per reach.  SHUD_WB_DIAG with --reorder is refused (its basin sums would run in another order), and so are lake
 // models.  Without the flag the program makes exactly the calls it made before.
-// Not restated (out of the device path's scope): the screen print, NetCDF forcing and outputs, the uncoupled -g
-// mode.
+// OUTPUT_MODE NETCDF / BOTH of <prj>.cfg.para (with NCOUTPUT_CFG): the NetCDF outputs of MD_initialize.cpp:346-371 on the
+// device (include/shud_out.h, include/shud_nc.h).  <prj>.ele.nc / .riv.nc / .lake.nc go to OUT_DIR of the ncoutput cfg,
+// else beside the .dat files; every print control whose NumAll is NumEle gets an element sink, else NumRiv a river
+// sink, else NumLake a lake sink (the reference's rule, in its order); NETCDF writes no .dat / .csv.  The files are in
+// the classic 64-bit-offset container (the reference: NetCDF-4 classic model), same names, types and attributes.  The
+// environment variable SHUD_NC_HISTORY replaces the whole `history` attribute ("<UTC now>: created by SHUD"), so that
+// files are reproducible.  With --reorder the slab is built from the control's buffer, which is in the input's column
+// order already.  A project without the key makes exactly the calls it made before.
+// Not restated (out of the device path's scope): the screen print, NetCDF forcing, the uncoupled -g mode.
 #include <strings.h>
 #include <sys/stat.h>
 
@@ -79,7 +86,10 @@ static void usage() {
                     "  --reorder ORDER run the device side in a planned element order (neighbours close in memory);\n"
                     "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n"
                     "                  tiles: breadth-first pockets that each fill one 256-element sharing tile;\n"
-                    "                  the faster one at every mesh size measured (prefer it).  bfs: plain breadth-first.\n");
+                    "                  the faster one at every mesh size measured (prefer it).  bfs: plain breadth-first.\n"
+                    "  OUTPUT_MODE NETCDF | BOTH with NCOUTPUT_CFG in <project>.cfg.para writes <project>.ele.nc, .riv.nc and\n"
+                    "                  .lake.nc (classic 64-bit-offset NetCDF); the environment variable SHUD_NC_HISTORY\n"
+                    "                  replaces their `history` attribute (default: \"<UTC now>: created by SHUD\").\n");
 }
 
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
@@ -277,6 +287,27 @@ int main(int argc, char **argv) {
     shud_rhs_summary(h, d_y);
     shud_out_t out = nullptr;
     shud_out_create(0, shud_rhs_stream(h), &out);
+    // ---- NetcdfOutputContext (MD_initialize.cpp:346-347): the three files, attached when the mode asks for them ----
+    ShudNcOutputCfg ncc;
+    shud_project_ncoutput(p, &ncc);
+    static const char *mode_name[3] = {"LEGACY", "NETCDF", "BOTH"};
+    if (!quiet) printf("* \t OUTPUT_MODE: %s\n", mode_name[ncc.output_mode]);      // Model_Control.cpp:641-643
+    if (ncc.output_mode != 0) {
+        int64_t nnode = 0;
+        const double *node_x = shud_project_node_xy(p, 0, &nnode), *node_y = shud_project_node_xy(p, 1, nullptr);
+        const char *hist = getenv("SHUD_NC_HISTORY");
+        const int n_of[SHUD_NC_KINDS] = {mesh.num_ele, mesh.num_riv, mesh.num_lake};
+        for (int k = 0; k < SHUD_NC_KINDS; k++) {
+            if (k != SHUD_NC_ELE && n_of[k] <= 0) continue;
+            ShudNcSpec ns = {k, n_of[k], ncc.out_dir, (int64_t)c.forc_start_time, hist && hist[0] ? hist : nullptr,
+                             ncc.crs_wkt, (int32_t)nnode, node_x, node_y, shud_project_ele_nodes(p, nullptr),
+                             shud_project_array(p, "x", nullptr), shud_project_array(p, "y", nullptr)};
+            if (shud_out_attach_nc(out, &ns)) {
+                fprintf(stderr, "shud_out_attach_nc: %s\n", shud_rhs_last_error_string());
+                return 1;
+            }
+        }
+    }
     const int nd = shud_project_outputs(p, outdir.c_str(), nullptr, 0);
     std::vector<ShudOutputDecl> decl(nd);
     shud_project_outputs(p, outdir.c_str(), decl.data(), nd);
@@ -299,11 +330,25 @@ int main(int argc, char **argv) {
                     mesh.num_ele);
             return 1;
         }
-        if (mapped ? shud_out_add_mapped(out, &ps, inv.data()) : shud_out_add(out, &ps)) {
+        // setSink (MD_initialize.cpp:348-356): by NumAll, elements first, then reaches, then lakes
+        int kind = -1;
+        if (ncc.output_mode != 0) {
+            if (d.n_all == mesh.num_ele) kind = SHUD_NC_ELE;
+            else if (mesh.num_riv > 0 && d.n_all == mesh.num_riv) kind = SHUD_NC_RIV;
+            else if (mesh.num_lake > 0 && d.n_all == mesh.num_lake) kind = SHUD_NC_LAKE;
+        }
+        if (ncc.output_mode == 1) ps.binary = ps.ascii = 0;          // open_file(0, 0, ...) (:362-363)
+        if (kind >= 0 ? shud_out_add_nc(out, &ps, mapped ? inv.data() : nullptr, kind, ncc.output_mode == 2)
+                      : (mapped ? shud_out_add_mapped(out, &ps, inv.data()) : shud_out_add(out, &ps))) {
             fprintf(stderr, "shud_out_add(%s): %s\n", d.basename, shud_rhs_last_error_string());
             return 1;
         }
         nprint++;
+    }
+    // the NetCDF headers and fixed variables (the mesh): before the time loop, not inside its first export
+    if (ncc.output_mode != 0 && shud_out_nc_begin(out)) {
+        fprintf(stderr, "shud_out_nc_begin: %s\n", shud_rhs_last_error_string());
+        return 1;
     }
 
     // ---- WaterBalanceDiag::enable (shud.cpp:70-75): shud.cpp:72's test, then openFiles' env_truthy ----

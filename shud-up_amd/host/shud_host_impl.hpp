@@ -82,6 +82,13 @@ struct Project {
     long long base_days = 0;
     bool base_ok = false;
     std::vector<std::string> out_names;
+    // OUTPUT_MODE / NCOUTPUT_CFG (Model_Control.cpp:229-266, 591-634) and the parsed ncoutput cfg
+    // (NetcdfOutputContext.cpp:1093-1153); warnings: the reference's stderr warnings of these keys, one per line
+    int output_mode = 0;                         // 0 LEGACY, 1 NETCDF, 2 BOTH
+    std::string ncoutput_cfg, nc_out_dir, nc_crs_wkt, nc_schema, nc_warnings;
+    // mesh as the UGRID variables of <prj>.ele.nc want it: node coordinates by node index, element nodes 1-based
+    std::vector<double> node_x, node_y;
+    std::vector<int32_t> ele_nodes;              // [NE][3]
 };
 
 int fail(Project *p, const char *fmt, ...);

@@ -7,7 +7,9 @@
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <set>
+#include <sstream>
 
 #include "shud_host_impl.hpp"
 #include "shud_out.h"
@@ -100,6 +102,80 @@ static int read_calib(Project &p) {
     return 0;
 }
 
+static void warn(Project &p, const char *fmt, ...) {
+    char buf[2048];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "%s\n", buf);
+    p.nc_warnings += buf;
+    p.nc_warnings += "\n";
+}
+
+// isAbsPath / dirnameOf / joinPath (NetcdfOutputContext.cpp:47-94)
+static bool is_abs_path(const std::string &s) {
+    if (s.empty()) return false;
+    if (s[0] == '/' || s[0] == '\\') return true;
+    return s.size() >= 2 && isalpha((unsigned char)s[0]) && s[1] == ':';
+}
+static std::string dirname_of(const std::string &s) {
+    const size_t pos = s.find_last_of("/\\");
+    if (pos == std::string::npos) return ".";
+    if (pos == 0) return "/";
+    return s.substr(0, pos);
+}
+static std::string join_path(const std::string &a, const std::string &b) {
+    if (a.empty()) return b;
+    if (b.empty()) return a;
+    return a.back() == '/' ? a + b : a + "/" + b;
+}
+
+// parseNcOutputCfg + the NetcdfOutputContext constructor's warnings (NetcdfOutputContext.cpp:110-143, 1093-1153):
+// KEY VALUE lines (keys in any case, '#' and blank lines skipped, a key without a value is an error); relative
+// values resolve against the run directory, the parent of the input directory's parent
+static int read_ncoutput_cfg(Project &p) {
+    std::ifstream f(p.ncoutput_cfg);
+    if (!f.is_open()) return fail(&p, "Fatal Error: Failed to open NetCDF output cfg. File: %s", p.ncoutput_cfg.c_str());
+    std::map<std::string, std::string> kv;
+    std::string line;
+    long line_no = 0;
+    while (std::getline(f, line)) {
+        line_no++;
+        const size_t first = line.find_first_not_of(" \t\r\n");
+        if (first == std::string::npos || line[first] == '#') continue;
+        std::istringstream iss(line);
+        std::string k, v;
+        if (!(iss >> k)) continue;
+        if (!(iss >> v))
+            return fail(&p, "Fatal Error: Invalid KEY VALUE ncoutput cfg line (missing value). File: %s Line: %ld "
+                        "Content: %s", p.ncoutput_cfg.c_str(), line_no, line.c_str());
+        kv[upper(k.c_str())] = v;
+    }
+    const std::string run_dir = dirname_of(dirname_of(dirname_of(p.ncoutput_cfg)));
+    auto get = [&](const char *k) {
+        const auto it = kv.find(k);
+        if (it == kv.end() || it->second.empty()) return std::string();
+        return is_abs_path(it->second) ? it->second : join_path(run_dir, it->second);
+    };
+    p.nc_schema = get("SCHEMA");
+    p.nc_out_dir = get("OUT_DIR");
+    const std::string crs = get("CRS_WKT");
+    if (!p.nc_schema.empty())
+        warn(p, "WARNING: NCOUTPUT_CFG SCHEMA is currently ignored (not implemented): %s", p.nc_schema.c_str());
+    if (!crs.empty()) {
+        std::ifstream fc(crs);
+        if (!fc.is_open()) return fail(&p, "Fatal Error: Failed to open CRS_WKT. File: %s", crs.c_str());
+        std::ostringstream ss;
+        ss << fc.rdbuf();
+        p.nc_crs_wkt = ss.str();
+    } else {
+        warn(p, "WARNING: NetCDF element outputs do not embed CRS information. Set NCOUTPUT_CFG CRS_WKT <path> to "
+             "include a WKT CRS.");
+    }
+    return 0;
+}
+
 // Control_Data::read (Model_Control.cpp:141-502) for the keys the device path uses, then updateSimPeriod
 // (:132-137).  Output intervals: PrintOutDt (Model_Control.hpp:116-147).
 static int read_para(Project &p, double end_day) {
@@ -179,10 +255,44 @@ static int read_para(Project &p, double end_day) {
                 fclose(fp);
                 return fail(&p, "FORCING_MODE NETCDF is out of scope (NetCDF forcing provider); use CSV forcing");
             }
+        } else if (is("OUTPUT_MODE")) {                                        // Model_Control.cpp:229-257
+            p.output_mode = 0;
+            if (sscanf(str, "%s %s", opt, mode) != 2) {
+                warn(p, "WARNING: OUTPUT_MODE missing value in %s; using default LEGACY (%d).", fn.c_str(), 0);
+            } else if (strcasecmp(mode, "LEGACY") == 0) p.output_mode = 0;
+            else if (strcasecmp(mode, "NETCDF") == 0) p.output_mode = 1;
+            else if (strcasecmp(mode, "BOTH") == 0) p.output_mode = 2;
+            else {
+                char *e = nullptr;
+                const double mv = strtod(mode, &e);
+                if (e && *e == '\0' && (mv == 0.0 || mv == 1.0 || mv == 2.0)) p.output_mode = (int)mv;
+                else {
+                    fclose(fp);
+                    return fail(&p, "ERROR: invalid OUTPUT_MODE value '%s' in %s. Valid values: LEGACY/NETCDF/BOTH or "
+                                "0/1/2.", mode, fn.c_str());
+                }
+            }
+        } else if (is("NCOUTPUT_CFG")) {                                       // :258-266
+            if (sscanf(str, "%s %s", opt, mode) != 2) {
+                fclose(fp);
+                return fail(&p, "ERROR: NCOUTPUT_CFG missing value in %s.", fn.c_str());
+            }
+            p.ncoutput_cfg = mode;
         }
-        // other keys (SCR_INTV, NUM_OPENMP, SpinupDay, OUTPUT_MODE, ...) do not reach the device path
+        // other keys (SCR_INTV, NUM_OPENMP, SpinupDay, ...) do not reach the device path
     }
     fclose(fp);
+    if (p.output_mode != 0) {                                                  // :591-634
+        if (p.ncoutput_cfg.empty())
+            return fail(&p, "ERROR: OUTPUT_MODE includes NETCDF and requires NCOUTPUT_CFG <path> in %s (relative paths "
+                        "are relative to the input directory).", fn.c_str());
+        if (!is_abs_path(p.ncoutput_cfg)) p.ncoutput_cfg = dirname_of(fn) + "/" + p.ncoutput_cfg;
+        FILE *fc = fopen(p.ncoutput_cfg.c_str(), "r");
+        if (!fc) return fail(&p, "ERROR: NCOUTPUT_CFG is not readable: %s (from %s).", p.ncoutput_cfg.c_str(), fn.c_str());
+        fclose(fc);
+        const int rc = read_ncoutput_cfg(p);
+        if (rc) return rc;
+    }
     if (end_day >= 0) day_end = end_day;
     c.solver_step = c.max_step;                                             // Model_Control.cpp:502
     c.start_time = day_start * 1440;                                        // updateSimPeriod
@@ -294,9 +404,19 @@ int load(Project &p, const char *indir, const char *prj, const char *cwd, double
     p.edge.resize(3 * (size_t)NE); p.d2e.resize(3 * (size_t)NE); p.d2n.resize(3 * (size_t)NE);
     p.avg_rough.resize(3 * (size_t)NE); p.nabr.resize(3 * (size_t)NE);
     p.nx.resize(NE); p.ny.resize(NE); p.nz.resize(NE); p.slope_angle.resize(NE); p.aspect.resize(NE);
+    // the UGRID view of <prj>.ele.nc (NetcdfOutputContext.cpp:528-556): node coordinates placed by the node's own
+    // index, element nodes as the file numbers them
+    p.node_x.assign(NN, 0.0); p.node_y.assign(NN, 0.0); p.ele_nodes.resize(3 * (size_t)NE);
+    for (int k = 0; k < NN; k++) {
+        const int idx = (int)nodes.at(k, 0);
+        if (idx < 1 || idx > NN) return fail(&p, "invalid node index %d (NumNode=%d)", idx, NN);
+        p.node_x[idx - 1] = nodes.at(k, 1);
+        p.node_y[idx - 1] = nodes.at(k, 2);
+    }
     for (int i = 0; i < NE; i++) {
         int nd[3];
         for (int j = 0; j < 3; j++) {
+            p.ele_nodes[3 * (size_t)i + j] = (int32_t)mesh.at(i, 1 + j);
             nd[j] = (int)mesh.at(i, 1 + j) - 1;                               // Node[node[k] - 1]: positional
             if (nd[j] < 0 || nd[j] >= NN) return fail(&p, "element %d: node %d out of range", i + 1, nd[j] + 1);
             const int nb = (int)mesh.at(i, 4 + j) - 1;
@@ -570,6 +690,34 @@ int shud_project_wb_interval(shud_project_t h) {
     if (p.dt_qe_et > 0) return p.dt_qe_et;
     if (p.dt_ye_surf > 0) return p.dt_ye_surf;
     return 1440;
+}
+
+int shud_project_ncoutput(shud_project_t h, ShudNcOutputCfg *c) {
+    if (!h || !c) return fail(nullptr, "null argument");
+    const Project &p = *reinterpret_cast<Project *>(h);
+    c->output_mode = p.output_mode;
+    c->ncoutput_cfg = p.output_mode ? p.ncoutput_cfg.c_str() : "";
+    c->out_dir = p.nc_out_dir.c_str();
+    c->crs_wkt = p.nc_crs_wkt.c_str();
+    c->schema = p.nc_schema.c_str();
+    c->warnings = p.nc_warnings.c_str();
+    return 0;
+}
+
+const double *shud_project_node_xy(shud_project_t h, int which, int64_t *n) {
+    if (n) *n = 0;
+    if (!h || which < 0 || which > 1) return nullptr;
+    const Project &p = *reinterpret_cast<Project *>(h);
+    if (n) *n = (int64_t)p.node_x.size();
+    return which ? p.node_y.data() : p.node_x.data();
+}
+
+const int32_t *shud_project_ele_nodes(shud_project_t h, int64_t *n) {
+    if (n) *n = 0;
+    if (!h) return nullptr;
+    const Project &p = *reinterpret_cast<Project *>(h);
+    if (n) *n = (int64_t)p.NE;
+    return p.ele_nodes.data();
 }
 
 int shud_project_update_ic_step(shud_project_t h) {

@@ -248,7 +248,39 @@ OUT_FUNCTIONS = {
     "shud_out_rows": (C.c_int64, [_H, C.c_int]),
     "shud_out_flush": (C.c_int, [_H]),
     "shud_out_destroy": (C.c_int, [_H]),
+    "shud_out_add_nc": (C.c_int, [_H, C.POINTER(ShudPrintSpec), c_int32_p, C.c_int32, C.c_int32]),
+    "shud_out_nc_begin": (C.c_int, [_H]),
+    "shud_out_time_nc": (C.c_int, [_H, C.c_int, C.c_int, c_double_p]),
 }
+
+# ---- include/shud_nc.h (classic-NetCDF writer of OUTPUT_MODE NETCDF / BOTH; device-free) ----
+SHUD_NC_ELE, SHUD_NC_RIV, SHUD_NC_LAKE = 0, 1, 2
+SHUD_NC_FILL_BITS = 0x7cf00000
+
+
+class ShudNcSpec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_all", C.c_int32), ("out_dir", C.c_char_p), ("forc_start_time", C.c_int64),
+                ("history", C.c_char_p), ("crs_wkt", C.c_char_p), ("num_node", C.c_int32), ("node_x", c_double_p),
+                ("node_y", c_double_p), ("face_nodes", c_int32_p), ("face_x", c_double_p), ("face_y", c_double_p)]
+
+
+NC_FUNCTIONS = {
+    "shud_nc_create": (C.c_int, [C.POINTER(ShudNcSpec), C.POINTER(_H)]),
+    "shud_nc_add_var": (C.c_int, [_H, C.c_char_p, C.c_int32, C.c_int64, c_int32_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "shud_nc_begin": (C.c_int, [_H]),
+    "shud_nc_record": (C.c_int, [_H, C.c_double, C.POINTER(C.c_int64)]),
+    "shud_nc_reserve": (C.c_int, [_H, C.c_double, C.POINTER(C.c_int64)]),
+    "shud_nc_put_slab": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_void_p]),
+    "shud_nc_put": (C.c_int, [_H, C.c_int32, C.c_double, c_double_p, C.c_int32]),
+    "shud_nc_convert": (C.c_int, [c_double_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "shud_nc_num_ctrl": (C.c_int32, [_H]),
+    "shud_nc_ctrl_var": (C.c_int32, [_H, C.c_int32]),
+    "shud_nc_num_records": (C.c_int64, [_H]),
+    "shud_nc_path": (C.c_char_p, [_H]),
+    "shud_nc_close": (C.c_int, [_H]),
+    "shud_nc_last_error": (C.c_char_p, []),
+}
+OUT_FUNCTIONS["shud_out_attach_nc"] = (C.c_int, [_H, C.POINTER(ShudNcSpec)])
 
 # ---- include/shud_wb.h (water-balance diagnostics on the device) ----
 (SHUD_WB_P, SHUD_WB_ET, SHUD_WB_QOUT, SHUD_WB_QEDGE, SHUD_WB_QBC, SHUD_WB_QSS, SHUD_WB_NONCONS, SHUD_WB_NBASIN) = range(8)
@@ -345,7 +377,8 @@ def bind(lib, strict=True):
     """set the signatures; strict=False (A/B builds of older sources) skips symbols the library lacks"""
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
                               + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())
-                              + list(MON_FUNCTIONS.items()) + list(ORDER_FUNCTIONS.items())):
+                              + list(MON_FUNCTIONS.items()) + list(ORDER_FUNCTIONS.items())
+                              + list(NC_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

@@ -36,6 +36,11 @@ class ShudOutputDecl(C.Structure):
                 ("interval", C.c_int32), ("iflux", C.c_int32), ("flag_io", C.POINTER(C.c_int32))]
 
 
+class ShudNcOutputCfg(C.Structure):
+    _fields_ = [("output_mode", C.c_int32), ("ncoutput_cfg", C.c_char_p), ("out_dir", C.c_char_p),
+                ("crs_wkt", C.c_char_p), ("schema", C.c_char_p), ("warnings", C.c_char_p)]
+
+
 _H = C.c_void_p
 
 
@@ -57,6 +62,9 @@ def lib():
             "shud_project_wb_interval": (C.c_int, [_H]),
             "shud_project_update_ic_step": (C.c_int, [_H]),
             "shud_project_riv_type": (C.POINTER(C.c_int32), [_H, C.POINTER(C.c_int64)]),
+            "shud_project_ncoutput": (C.c_int, [_H, C.POINTER(ShudNcOutputCfg)]),
+            "shud_project_node_xy": (C.POINTER(C.c_double), [_H, C.c_int, C.POINTER(C.c_int64)]),
+            "shud_project_ele_nodes": (C.POINTER(C.c_int32), [_H, C.POINTER(C.c_int64)]),
             "shud_project_forcing": (C.c_int, [_H, C.c_double, C.c_double, C.POINTER(abi.ShudEtForcing)]),
             "shud_project_bc_rows": (C.c_int, [_H, C.POINTER(abi.ShudStepInputs)]),
             "shud_project_solar": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -168,6 +176,22 @@ class Project:
         p = lib().shud_project_riv_type(self.h, C.byref(n))
         a = _arr(p, n.value, np.int32)
         return np.zeros(0, dtype=np.int32) if a is None else a
+
+    def ncoutput(self):
+        """OUTPUT_MODE (0 LEGACY, 1 NETCDF, 2 BOTH) and the parsed NCOUTPUT_CFG: dict(output_mode, ncoutput_cfg,
+        out_dir, crs_wkt (the file's text), schema, warnings)"""
+        c = ShudNcOutputCfg()
+        lib().shud_project_ncoutput(self.h, C.byref(c))
+        return {k: (getattr(c, k).decode() if t is C.c_char_p else getattr(c, k)) for k, t in ShudNcOutputCfg._fields_}
+
+    def mesh_nodes(self):
+        """the UGRID arrays of <prj>.ele.nc: node_x / node_y by node index, face_nodes [NumEle, 3] 1-based, face_x /
+        face_y (element centroids) -- the `mesh` argument of runtime.Output.attach_nc"""
+        n = C.c_int64()
+        x = _arr(lib().shud_project_node_xy(self.h, 0, C.byref(n)), n.value, np.float64)
+        y = _arr(lib().shud_project_node_xy(self.h, 1, C.byref(n)), n.value, np.float64)
+        fn = _arr(lib().shud_project_ele_nodes(self.h, C.byref(n)), 3 * n.value, np.int32)
+        return dict(node_x=x, node_y=y, face_nodes=fn.reshape(-1, 3), face_x=self.array("x"), face_y=self.array("y"))
 
     def bc_rows(self):
         """{ele_ybc, ele_qbc, riv_ybc, riv_qbc} rows at the current ET step (model.step_struct bc_tables form:

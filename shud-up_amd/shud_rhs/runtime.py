@@ -463,8 +463,10 @@ class Output:
 
     def add(self, basename, d_src, n_all, interval, iflux, start_time=0, flag_io=None, binary=True, ascii=False,
             radiation_input_mode=0, terrain_radiation=0, solar_lonlat_mode="FORCING_FIRST", lon=0.0, lat=0.0,
-            col_src=None):
-        """col_src [n_all]: column c reads d_src[col_src[c]] (shud_out_add_mapped); flag_io stays by column c"""
+            col_src=None, nc=None, legacy=True):
+        """col_src [n_all]: column c reads d_src[col_src[c]] (shud_out_add_mapped); flag_io stays by column c.
+        nc: "ele" / "riv" / "lake" = a NetCDF sink in the attached file of that kind (shud_out_add_nc); legacy=False
+        (OUTPUT_MODE NETCDF) writes no .dat / .csv beside it."""
         flags = None if flag_io is None else np.ascontiguousarray(flag_io, dtype=np.int32)
         cmap = None if col_src is None else np.ascontiguousarray(col_src, dtype=np.int32)
         assert cmap is None or cmap.size == int(n_all)
@@ -472,13 +474,35 @@ class Output:
         spec = abi.ShudPrintSpec(bn, C.c_void_p(d_src), int(n_all), None if flags is None else flags.ctypes.data,
                                  int(interval), int(iflux), int(start_time), int(bool(binary)), int(bool(ascii)),
                                  int(radiation_input_mode), int(terrain_radiation), sm, float(lon), float(lat))
-        if cmap is None:
+        if nc is not None:
+            kind = {"ele": abi.SHUD_NC_ELE, "riv": abi.SHUD_NC_RIV, "lake": abi.SHUD_NC_LAKE}[nc]
+            _check(lib().shud_out_add_nc(self.h, C.byref(spec), None if cmap is None else
+                                         cmap.ctypes.data_as(abi.c_int32_p), kind, int(bool(legacy))),
+                   "shud_out_add_nc")
+        elif cmap is None:
             _check(lib().shud_out_add(self.h, C.byref(spec)), "shud_out_add")
         else:
             _check(lib().shud_out_add_mapped(self.h, C.byref(spec), cmap.ctypes.data_as(abi.c_int32_p)),
                    "shud_out_add_mapped")
         self._keep.append((bn, sm, flags))
         return len(self._keep) - 1
+
+    def attach_nc(self, kind, n_all, forc_start_time, out_dir=None, history=None, crs_wkt=None, mesh=None):
+        """attach the NetCDF file of `kind` ("ele", "riv", "lake"; include/shud_nc.h) for add(nc=kind).  out_dir: OUT_DIR
+        of the ncoutput cfg (None: beside the legacy files); history: the whole `history` attribute (None: "<UTC now>:
+        created by SHUD"); crs_wkt: the WKT text; mesh (kind "ele"): host.Project.mesh_nodes()"""
+        spec, keep = nc_spec(kind, n_all, forc_start_time, out_dir, history, crs_wkt, mesh)
+        _check(lib().shud_out_attach_nc(self.h, C.byref(spec)), "shud_out_attach_nc")
+
+    def nc_begin(self):
+        """write the NetCDF headers now (otherwise at the first export)"""
+        _check(lib().shud_out_nc_begin(self.h), "shud_out_nc_begin")
+
+    def time_nc(self, k, reps):
+        """device ms per launch of control k's interval-end kernel (shud_out_time_nc; zeroes its accumulator)"""
+        ms = C.c_double()
+        _check(lib().shud_out_time_nc(self.h, int(k), int(reps), C.byref(ms)), "shud_out_time_nc")
+        return ms.value
 
     def export(self, t):
         _check(lib().shud_out_export(self.h, float(t)), "shud_out_export")
@@ -502,6 +526,85 @@ class Output:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def _nc_check(rc, what):
+    if rc != abi.SHUD_OK:
+        raise ShudRhsError(rc, f"{what}: {lib().shud_nc_last_error().decode(errors='replace')}")
+
+
+def nc_spec(kind, n_all, forc_start_time, out_dir=None, history=None, crs_wkt=None, mesh=None):
+    """abi.ShudNcSpec and the arrays it points at (keep both alive while the spec is in use).  kind: "ele", "riv",
+    "lake"; mesh (kind "ele"): dict(node_x, node_y, face_nodes [n_all, 3] 1-based, face_x, face_y)."""
+    k = {"ele": abi.SHUD_NC_ELE, "riv": abi.SHUD_NC_RIV, "lake": abi.SHUD_NC_LAKE}[kind]
+    enc = lambda v: None if v is None else str(v).encode()
+    keep = [enc(out_dir), enc(history), enc(crs_wkt)]
+    s = abi.ShudNcSpec(k, int(n_all), keep[0], int(forc_start_time), keep[1], keep[2], 0, None, None, None, None, None)
+    if kind == "ele":
+        d = [np.ascontiguousarray(mesh[n], dtype=np.float64) for n in ("node_x", "node_y", "face_x", "face_y")]
+        fn = np.ascontiguousarray(mesh["face_nodes"], dtype=np.int32).reshape(-1)
+        assert d[0].size == d[1].size and d[2].size == d[3].size == int(n_all) and fn.size == 3 * int(n_all)
+        s.num_node = d[0].size
+        s.node_x, s.node_y, s.face_x, s.face_y = (a.ctypes.data_as(abi.c_double_p) for a in d)
+        s.face_nodes = fn.ctypes.data_as(abi.c_int32_p)
+        keep += d + [fn]
+    return s, keep
+
+
+class NcFile:
+    """One NetCDF output file written on the host (include/shud_nc.h): the reference's NetcdfElementFile /
+    NetcdfSimpleFile in the classic 64-bit-offset container.  add_var() = a sink's onInit, put() = its onWrite."""
+
+    def __init__(self, kind, n_all, forc_start_time, out_dir=None, history=None, crs_wkt=None, mesh=None):
+        spec, keep = nc_spec(kind, n_all, forc_start_time, out_dir, history, crs_wkt, mesh)
+        h = C.c_void_p()
+        _nc_check(lib().shud_nc_create(C.byref(spec), C.byref(h)), "shud_nc_create")
+        self.h, self.n_all, self.forc_start_time = h, int(n_all), int(forc_start_time)
+
+    def add_var(self, basename, icol, n_all=None):
+        """icol: selected columns, 1-based; returns the control's id"""
+        ic = np.ascontiguousarray(icol, dtype=np.int32)
+        k = C.c_int32()
+        _nc_check(lib().shud_nc_add_var(self.h, str(basename).encode(), self.n_all if n_all is None else int(n_all),
+                                        self.forc_start_time, ic.ctypes.data_as(abi.c_int32_p), ic.size, C.byref(k)),
+                  "shud_nc_add_var")
+        return k.value
+
+    def put(self, ctrl, t_quantized, selected):
+        v = np.ascontiguousarray(selected, dtype=np.float64)
+        _nc_check(lib().shud_nc_put(self.h, int(ctrl), float(t_quantized), v.ctypes.data_as(abi.c_double_p), v.size),
+                  "shud_nc_put")
+
+    @property
+    def path(self):
+        return lib().shud_nc_path(self.h).decode()
+
+    @property
+    def num_records(self):
+        return lib().shud_nc_num_records(self.h)
+
+    def close(self):
+        if self.h:
+            rc = lib().shud_nc_close(self.h)
+            self.h = None
+            _nc_check(rc, "shud_nc_close")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def nc_convert(selected, icol, n_all):
+    """the host conversion of a NetCDF put: the n_all slab words as they go to disk (big-endian float, fill at
+    unselected positions), as a '>f4' array"""
+    v = np.ascontiguousarray(selected, dtype=np.float64)
+    ic = np.ascontiguousarray(icol, dtype=np.int32)
+    out = np.empty(int(n_all), dtype=">f4")
+    _nc_check(lib().shud_nc_convert(v.ctypes.data_as(abi.c_double_p), v.size, ic.ctypes.data_as(abi.c_int32_p), ic.size,
+                                    int(n_all), out.ctypes.data), "shud_nc_convert")
+    return out
 
 
 class WaterBalance:

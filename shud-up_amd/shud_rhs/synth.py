@@ -263,12 +263,15 @@ def synth_raw(n_target, seed=12345, h=100.0, stem_every=12, reach_quads=3):
 
 
 def write_project(outdir, prj, n_target, days=2.0, seed=12345, max_step=10.0, et_step=60.0, dt_out=60,
-                  forcing_dt_min=60.0, extra_para=None, bc=False, cfg_output=False, lake=False):
+                  forcing_dt_min=60.0, extra_para=None, bc=False, cfg_output=False, lake=False, output_mode=None,
+                  ncoutput_cfg=None):
     """Write input files <outdir>/<prj>.* for the synthetic mesh; returns the in-memory ShudModel.
     bc: a few elements / reaches get boundary conditions (iBC = +-1, +-2; BC = +-1) with hourly .tsd.ebc1/.ebc2/
     .rbc1/.rbc2 tables.  cfg_output: a .cfg.output switching some element / reach columns off.
     lake: one lake (iLake = 1, MD_readin.cpp:262-263) over a 10 x 10-quad patch of the mesh, with a three-row
-    <prj>.lake.bathy (MD_Lake.cpp:147-168) and its stage as the cfg.ic's third table."""
+    <prj>.lake.bathy (MD_Lake.cpp:147-168) and its stage as the cfg.ic's third table.
+    output_mode / ncoutput_cfg: the OUTPUT_MODE and NCOUTPUT_CFG keys of cfg.para (written only when given; the
+    ncoutput cfg file itself is the caller's)."""
     os.makedirs(outdir, exist_ok=True)
     m, raw = synth_raw(n_target, seed=seed)
     NE, NR, NS = m.num_ele, m.num_riv, m.num_seg
@@ -331,6 +334,10 @@ def write_project(outdir, prj, n_target, days=2.0, seed=12345, max_step=10.0, et
             "dt_qe_prcp": dt_out, "dt_qe_infil": dt_out, "dt_qe_rech": dt_out, "dt_Qe_sub": dt_out,
             "dt_Qe_surf": dt_out, "dt_yr_stage": dt_out, "dt_Qr_down": dt_out, "dt_Qr_up": dt_out,
             "dt_Qr_surf": dt_out, "dt_Qr_sub": dt_out}
+    if output_mode is not None:
+        para["OUTPUT_MODE"] = output_mode
+    if ncoutput_cfg is not None:
+        para["NCOUTPUT_CFG"] = ncoutput_cfg
     para.update(extra_para or {})
     with open(p("cfg.para"), "w") as f:
         for k, v in para.items():
