@@ -37,7 +37,7 @@ enum {
     SHUD_ARR_Y_ELE_UNSAT,        /* yEleUnsat                                    NE  */
     SHUD_ARR_Y_ELE_GW,           /* yEleGW (yBC where iBC > 0)                   NE  */
     SHUD_ARR_Y_RIV_STG,          /* yRivStg (Riv.yBC where BC > 0)              NR  */
-    SHUD_ARR_Y_LAKE_STG,         /* yLakeStg                                     NL  */
+    SHUD_ARR_Y_LAKE_STG,         /* yLakeStg: lake entries of the last RHS input NL  */
     /* fluxes of the last RHS evaluation (filled by shud_rhs_refresh_diagnostics) */
     SHUD_ARR_QELE_SURF_TOT,      /* QeleSurfTot                                  NE  */
     SHUD_ARR_QELE_SUB_TOT,       /* QeleSubTot                                   NE  */
@@ -50,8 +50,8 @@ enum {
     SHUD_ARR_Q_RECHARGE,         /* qEleRecharge                                 NE  */
     SHUD_ARR_Q_ETA,              /* qEleETA                                      NE  */
     SHUD_ARR_Q_E_IC,             /* qEleE_IC (as mutated by the last RHS)        NE  */
-    SHUD_ARR_Q_TRANS,            /* qEleTrans = qTu + qTg (MD_ET.cpp:384)       NE  */
-    SHUD_ARR_Q_EVAPO,            /* qEleEvapo = qEu + qEg + qEs (MD_ET.cpp:385) NE  */
+    SHUD_ARR_Q_TRANS,            /* qEleTrans = qTu + qTg; 0 on a lake element  NE  */
+    SHUD_ARR_Q_EVAPO,            /* qEleEvapo = qEu + qEg + qEs; qPotEvap on a lake element NE */
     SHUD_ARR_QRIV_DOWN,          /* QrivDown                                     NR  */
     SHUD_ARR_QRIV_UP,            /* QrivUp                                       NR  */
     SHUD_ARR_QRIV_SURF,          /* QrivSurf                                     NR  */
@@ -77,10 +77,12 @@ enum {
     SHUD_ARR_COUNT
 };
 
-/* fills the SHUD_ARR_Y_* arrays from y (device pointer, NY values; the Model_Data::summary step) */
+/* fills the SHUD_ARR_Y_* arrays from y (device pointer, NY values; the Model_Data::summary step).  yLakeStg is not
+ * summary's: the reference sets it in LoadIC and f_update (MD_update.cpp:175), so it is taken from y only before
+ * the handle's first evaluation (the initial condition) and by shud_rhs_refresh_diagnostics afterwards */
 int shud_rhs_summary(shud_rhs_t h, const double *d_y);
 /* replays the last RHS evaluation with diagnostic stores into the device arrays (no host copy; carried
- * state unchanged): what the reference's flux arrays hold after CVODE's last f() call */
+ * state unchanged): what the reference's flux arrays, yLakeStg and y2LakeArea hold after CVODE's last f() call */
 int shud_rhs_refresh_diagnostics(shud_rhs_t h);
 /* allocates every array above (zero-filled) without evaluating anything, so print controls can be registered
  * before the first RHS call (the serial RHS is stateful: an extra evaluation would change the trajectory) */

@@ -4,7 +4,7 @@ the synthetic BC project, each in a temporary directory.  The recordings are dat
 the tests compare against them on machines without the binaries, and against a fresh run where they exist.
 
     python oracle/ref/record.py            # everything
-    python oracle/ref/record.py rhs|kat|et
+    python oracle/ref/record.py rhs|kat|et|writers
 
 Every run uses a team of 1 thread: the driver overrides the reference's CS.num_threads (the archives' .cfg.para
 carry NUM_OPENMP 8, which would win over -n and OMP_NUM_THREADS) and dumps the team size it observed, which is
@@ -48,9 +48,41 @@ def record_et():
         print("et", [f"{os.path.basename(p)} {os.path.getsize(p)}" for p in paths])
 
 
+def record_writers():
+    """SHUD()'s loop with a scripted solver: output files, restart files, flood file, water-balance files"""
+    full = {}
+    for case, c in refio.WRITER_CASES.items():
+        with tempfile.TemporaryDirectory() as tmp:
+            rec = full[case] = refio.run_writer_case(case, tmp)
+        files = refio.writer_files(rec)
+        prj = c["prj"]
+        if "same_events_as" in c:
+            assert set(rec) <= set(full[c["same_events_as"]])
+        else:
+            flood, nriv = rec["x:flood"][:, 0], int(rec["dims"][2])
+            if case in ("ccw_w", "syn_w"):
+                # the flood file: some calls with rows for some reaches but not all, one call with none
+                rows = np.array([ln.split(b"\t")[0] for ln in files[f"{prj}.flood.csv"].split(b"\n")[1:] if ln])
+                per_call = [int((rows == (b"%.1f" % t)).sum()) for t in rec["ev_t"][rec["ev_kind"] == refio.EV_X]]
+                assert any(0 < n < nriv for n in per_call), per_call
+                if case == "ccw_w":
+                    assert (flood == 0).any() and b"-nan" in files["ccw.flood.csv"] + files["ccw.rivystage.csv"]
+                    assert b"inf" in files["ccw.flood.csv"]
+            if case == "qhh_w":                    # y_rhs and y_out differ in the lake entry of an exported step
+                ops = refio.writer_ops(rec)
+                fy = [op[2][-1] for op in ops if op[0] == "f"]
+                xy = [op[2][-1] for op in ops if op[0] == "x"]
+                assert fy[0] != xy[0] and fy[1] == xy[1]
+            del rec["script_y"]                     # rebuilt by refio.writer_script (deterministic)
+        paths = refio.save_recording(case, rec)
+        print(case, [f"{os.path.basename(p)} {os.path.getsize(p)}" for p in paths])
+
+
 if __name__ == "__main__":
     if not refio.have_ref():
         sys.exit("oracle/_ref/ holds no reference binaries: run `make -C oracle` with a reference checkout")
-    what = sys.argv[1:] or ["rhs", "kat", "et"]
+    what = sys.argv[1:] or ["rhs", "kat", "et", "writers"]
+    if "writers" in what and not refio.have_writer_ref():
+        sys.exit("oracle/_ref/shud_ref_f predates the driver's mode w: run `make -C oracle`")
     for w in what:
-        {"rhs": record_rhs, "kat": record_kat, "et": record_et}[w]()
+        {"rhs": record_rhs, "kat": record_kat, "et": record_et, "writers": record_writers}[w]()

@@ -17,6 +17,15 @@ O_PIC = $(addprefix _ref/obj/pic/,$(addsuffix .o,$(NAMES)))
 HDRS = $(wildcard $(SRC)/*/*.hpp) ref/nvector/nvector_serial.h ref/nvector/nvector_openmp.h
 
 all: _ref/shud_ref_f _ref/shud_ref_f_omp _ref/libshud_ref_kat.so
+# Our own units are rebuilt when their text changes, whatever the time stamps say: a checkout can leave a changed
+# source older than objects built from its earlier version, and a driver without the newer modes would run (and
+# exit 0) all the same.  The stamp holds a checksum of our sources and is rewritten only when it differs.
+OURS = ref/shud_ref_driver.cpp ref/shud_ref_kat.cpp ref/ref.mk ref/nvector/nvector_serial.h ref/nvector/nvector_openmp.h
+_ref/ours.stamp: FORCE
+	@mkdir -p _ref
+	@cat $(OURS) | cksum > $@.new; if cmp -s $@.new $@; then rm -f $@.new; else mv $@.new $@; fi
+FORCE:
+_ref/obj/ser/shud_ref_driver.o _ref/obj/omp/shud_ref_driver.o _ref/obj/pic/shud_ref_kat.o: _ref/ours.stamp
 _ref/obj/ser/%.o: %.cpp $(HDRS)
 	@mkdir -p $(@D)
 	$(CXX) $(REFFLAGS) $(INC) -c -o $@ $<
@@ -32,4 +41,4 @@ _ref/shud_ref_f_omp: _ref/obj/omp/shud_ref_driver.o $(O_OMP)
 	$(CXX) -fopenmp -o $@ $^ -lm
 _ref/libshud_ref_kat.so: _ref/obj/pic/shud_ref_kat.o $(O_PIC)
 	$(CXX) -shared -o $@ $^ -lm
-.PHONY: all
+.PHONY: all FORCE

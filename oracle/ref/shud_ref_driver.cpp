@@ -11,6 +11,19 @@
  *       in this one process (so the carried qEleE_IC / u_satn / uYgw advance as in a run), dumping DY per call.
  *   shud_ref_f et OUT -      N_ET THREADS <reference arguments>   ET-prelude mode
  *       runs N_ET ET steps and dumps the per-element prelude results after each.
+ *   shud_ref_f w  OUT SCRIPT 0    THREADS <reference arguments>   writers mode
+ *       SHUD()'s whole sequence (shud.cpp:69-157) with CVODE taken out: initialize_output, WaterBalanceDiag
+ *       (enabled by SHUD_WB_DIAG as there), PrintInit, InitFloodAlert, the loop over NumSteps / SolverStep with
+ *       the ET sub-step rule, summary, sample / maybeWrite, ExportResults, FloodWarning.  A CVode(...) call is
+ *       replaced by the next record of SCRIPT: the state is read into u, t is set to the record's time, and the
+ *       reference's f(t, u, du, MD) is called, so its flux arrays hold that call as after CVODE's last RHS
+ *       evaluation.  After the inner loop the next record is read into u (y(tout), as CVode returns it); with the
+ *       water balance on, the DY of the f() call shud.cpp makes there stands in for CVodeGetDky.  SCRIPT is a
+ *       sequence of records (kind, t, y[NumY]) of float64: kind 0 a CVode return, 2 a CV_ONE_STEP return
+ *       (SHUD_WB_DIAG_QUAD), 1 the state returned to summary (its t is not used).  The files the reference
+ *       writes into its output directory are the recording; every restart file is copied aside
+ *       (<name>.<k>) when PrintInit wrote it.  OUT gets the events in order: "ev_et" (step inputs after ET()),
+ *       "ev_f" (t of an f() call, BC rows), "ev_x" (the arrays the reference holds at ExportResults).
  *
  * THREADS: the OpenMP build's team size.  The reference takes max(NUM_OPENMP of <prj>.cfg.para, -n) and passes it
  * to every loop of MD_f_omp.cpp as num_threads(CS.num_threads), so neither OMP_NUM_THREADS nor -n can lower it;
@@ -41,6 +54,8 @@
 #include "IO.hpp"
 #include "Model_Data.hpp"
 #include "CommandIn.hpp"
+#include "FloodAlert.hpp"
+#include "WaterBalanceDiag.hpp"
 #undef private
 #undef protected
 
@@ -75,9 +90,184 @@ static void rec_tsd(const char *name, _TimeSeriesData &ts, double t) {
     rec(name, row.data(), (long)row.size());
 }
 
+static int g_ic_copies;
+static int print_init(Model_Data *MD, const char *fn, double t) {
+    const int wrote = MD->PrintInit(fn, t);
+    if (wrote) {                                       /* the file is overwritten by the next one: keep a copy */
+        std::ifstream src(fn, std::ios::binary);
+        std::ofstream dst(std::string(fn) + "." + std::to_string(g_ic_copies++), std::ios::binary);
+        dst << src.rdbuf();
+    }
+    return wrote;
+}
+static void rec_step_inputs(Model_Data *MD, double t, std::vector<double> &tmp) {
+    const int NE = MD->NumEle;
+    rec("ev_et", &t, 1);
+    rec("net_prep", MD->qEleNetPrep, NE);
+    rec("pot_evap", MD->qPotEvap, NE);
+    rec("pot_tran", MD->qPotTran, NE);
+    rec("etp", MD->qEleETP, NE);
+    rec("lai", MD->t_lai, NE);
+    rec("fu_surf", MD->fu_Surf, NE);
+    rec("fu_sub", MD->fu_Sub, NE);
+    rec("e_ic", MD->qEleE_IC, NE);
+    for (int i = 0; i < NE; i++) tmp[(size_t)i] = MD->Ele[i].u_satn;
+    rec("u_satn", tmp.data(), NE);
+    rec("ugw_stale", uYgw, NE);
+    rec("prcp", MD->qElePrep, NE);
+    rec("y_is", MD->yEleIS, NE);
+    rec("y_snow", MD->yEleSnow, NE);
+}
+static void rec_f(Model_Data *MD, double t) {
+    rec("ev_f", &t, 1);
+    if (MD->ieBC1 && MD->NumBCEle1 > 0) rec_tsd("ele_ybc", MD->tsd_eyBC, t);
+    if (MD->ieBC2 && MD->NumBCEle2 > 0) rec_tsd("ele_qbc", MD->tsd_eqBC, t);
+    if (MD->irBC1 && MD->NumBCRiv1 > 0) rec_tsd("riv_ybc", MD->tsd_ryBC, t);
+    if (MD->irBC2 && MD->NumBCRiv2 > 0) rec_tsd("riv_qbc", MD->tsd_rqBC, t);
+}
+static void rec_summary(Model_Data *MD) {
+    rec("y_surf", MD->yEleSurf, MD->NumEle);
+    rec("y_unsat", MD->yEleUnsat, MD->NumEle);
+    rec("y_gw", MD->yEleGW, MD->NumEle);
+    rec("y_riv", MD->yRivStg, MD->NumRiv);
+    rec("y_lake", MD->yLakeStg, MD->NumLake);
+}
+static void rec_export(Model_Data *MD, double t, std::vector<double> &tmp) {
+    const int NE = MD->NumEle, NR = MD->NumRiv, NL = MD->NumLake;
+    rec("ev_x", &t, 1);
+    rec_summary(MD);
+    std::vector<double> e3((size_t)(3 * NE));
+    for (int j = 0; j < 3; j++)
+        for (int i = 0; i < NE; i++) e3[(size_t)(j * NE + i)] = MD->QeleSurf[i][j];
+    rec("qele_surf", e3.data(), 3 * NE);
+    for (int j = 0; j < 3; j++)
+        for (int i = 0; i < NE; i++) e3[(size_t)(j * NE + i)] = MD->QeleSub[i][j];
+    rec("qele_sub", e3.data(), 3 * NE);
+    rec("qele_surf_tot", MD->QeleSurfTot, NE);
+    rec("qele_sub_tot", MD->QeleSubTot, NE);
+    rec("q_infil", MD->qEleInfil, NE);
+    rec("q_exfil", MD->qEleExfil, NE);
+    rec("q_recharge", MD->qEleRecharge, NE);
+    rec("q_es", MD->qEs, NE);
+    rec("q_eu", MD->qEu, NE);
+    rec("q_eg", MD->qEg, NE);
+    rec("q_tu", MD->qTu, NE);
+    rec("q_tg", MD->qTg, NE);
+    rec("q_eta", MD->qEleETA, NE);
+    rec("q_trans", MD->qEleTrans, NE);
+    rec("q_evapo", MD->qEleEvapo, NE);
+    rec("e_ic_f", MD->qEleE_IC, NE);
+    for (int i = 0; i < NE; i++) tmp[(size_t)i] = MD->Ele[i].u_satn;
+    rec("u_satn_f", tmp.data(), NE);
+    rec("qe2r_surf", MD->Qe2r_Surf, NE);
+    rec("qe2r_sub", MD->Qe2r_Sub, NE);
+    rec("qriv_down", MD->QrivDown, NR);
+    rec("qriv_up", MD->QrivUp, NR);
+    rec("qriv_surf", MD->QrivSurf, NR);
+    rec("qriv_sub", MD->QrivSub, NR);
+    rec("q_lake_surf", MD->QLakeSurf, NL);
+    rec("q_lake_sub", MD->QLakeSub, NL);
+    rec("q_lake_rivin", MD->QLakeRivIn, NL);
+    rec("q_lake_rivout", MD->QLakeRivOut, NL);
+    rec("q_lake_evap", MD->qLakeEvap, NL);
+    rec("q_lake_prcp", MD->qLakePrcp, NL);
+    rec("lake_toparea", MD->y2LakeArea, NL);
+    rec("rn_h", MD->ele_rn_h_wm2, MD->ele_rn_h_wm2 ? NE : 0);
+    rec("rn_t", MD->ele_rn_t_wm2, MD->ele_rn_t_wm2 ? NE : 0);
+    rec("rn_factor", MD->ele_rn_factor, MD->ele_rn_factor ? NE : 0);
+}
+/* the next record of the script: kind, t, y -> u */
+static int next_state(FILE *fs, N_Vector u, int NY, double *t) {
+    double head[2];
+    if (fread(head, sizeof(double), 2, fs) != 2 || fread(REF_DATA(u), sizeof(double), (size_t)NY, fs) != (size_t)NY) {
+        fprintf(stderr, "shud_ref_f w: the script ended early\n");
+        exit(3);
+    }
+    *t = head[1];
+    return (int)head[0];
+}
+static void expect(int kind, int want) {
+    if (kind != want) {
+        fprintf(stderr, "shud_ref_f w: script record of kind %d where %d is due\n", kind, want);
+        exit(3);
+    }
+}
+
+/* SHUD() of src/Model/shud.cpp from initialize_output() on, CVODE replaced by the script */
+static int run_writers(Model_Data *MD, FileOut *fout, N_Vector u, N_Vector du, const char *script) {
+    const int NY = MD->NumY, NE = MD->NumEle;
+    std::vector<double> tmp((size_t)NE);
+    FILE *fs = fopen(script, "rb");
+    if (!fs) { perror(script); return 2; }
+    MD->initialize_output();
+    WaterBalanceDiag wbdiag(MD);
+    const char *shud_wb_diag = getenv("SHUD_WB_DIAG");
+    if (shud_wb_diag != nullptr && shud_wb_diag[0] != '\0' && strcmp(shud_wb_diag, "0") != 0) {
+        wbdiag.enable();
+        MD->wbdiag = &wbdiag;
+    }
+    double flags[3] = {(double)wbdiag.isEnabled(), (double)wbdiag.quadEnabled(), (double)MD->CS.NumPrint};
+    rec("wb_flags", flags, 3);
+    double ctl[4] = {(double)MD->CS.NumSteps, MD->CS.SolverStep, MD->CS.ETStep, (double)MD->CS.UpdateICStep};
+    rec("control", ctl, 4);
+    rec("ev_x0", &MD->CS.StartTime, 1);
+    rec_summary(MD);
+    print_init(MD, fout->Init_bak, 0);
+    MD->InitFloodAlert(fout->floodout);
+    double t = MD->CS.StartTime, tnext = t;
+    const bool etSubstepEnabled = (MD->CS.ETStep > ZERO && MD->CS.ETStep + ZERO < MD->CS.SolverStep);
+    for (int i = 0; i < MD->CS.NumSteps; i++) {
+        print_init(MD, fout->Init_update, t);
+        tnext += MD->CS.SolverStep;
+        while (t + ZERO < tnext) {
+            double tout = tnext;
+            if (etSubstepEnabled) tout = min(t + MD->CS.ETStep, tnext);
+            MD->updateAllTimeSeries(t);
+            MD->updateforcing(t);
+            MD->ET(t, tout);
+            if (MD->wbdiag != nullptr) MD->wbdiag->onETUpdate();
+            rec_step_inputs(MD, t, tmp);
+            const bool wbdiagOneStepEnabled = (MD->wbdiag != nullptr && MD->wbdiag->quadEnabled());
+            if (wbdiagOneStepEnabled) {
+                while (t + ZERO < tout) {
+                    expect(next_state(fs, u, NY, &t), 2);          /* CVode(mem, tout, udata, &t, CV_ONE_STEP) */
+                    f(t, u, du, MD);
+                    rec_f(MD, t);
+                    MD->wbdiag->onCvodeMonitorStep(t);
+                }
+            } else {
+                expect(next_state(fs, u, NY, &t), 0);              /* CVode(mem, tout, udata, &t, CV_NORMAL) */
+                f(t, u, du, MD);
+                rec_f(MD, t);
+            }
+        }
+        double unused;
+        expect(next_state(fs, u, NY, &unused), 1);                 /* udata as CVode returned it */
+        MD->summary(u);
+        if (MD->wbdiag != nullptr) {
+            f(t, u, du, MD);
+            rec_f(MD, t);
+            MD->wbdiag->sample(t, REF_DATA(du));
+        }
+        if (MD->wbdiag != nullptr) MD->wbdiag->maybeWrite(t);
+        MD->CS.ExportResults(t);
+        const double flood = MD->flood->FloodWarning(t);
+        rec_export(MD, t, tmp);
+        rec("flood", &flood, 1);
+    }
+    print_init(MD, fout->Init_update, t);
+    fclose(fs);
+    double n_ic = g_ic_copies;
+    rec("ic_copies", &n_ic, 1);
+    fclose(g_out);
+    fflush(MD->flood->fid);
+    for (int i = 0; i < MD->CS.NumPrint; i++) MD->CS.PCtrl[i].close_file();
+    return 0;                                                    /* wbdiag's destructor closes its files */
+}
+
 int main(int argc, char **argv) {
     if (argc < 7) {
-        fprintf(stderr, "usage: %s f|et OUT STATES|- N_ET THREADS <reference arguments>\n", argv[0]);
+        fprintf(stderr, "usage: %s f|et|w OUT STATES|- N_ET THREADS <reference arguments>\n", argv[0]);
         return 2;
     }
     const std::string mode = argv[1];
@@ -125,6 +315,7 @@ int main(int argc, char **argv) {
     rec("ic_is", MD->yEleIS, NE);
     rec("ic_snow", MD->yEleSnow, NE);
 
+    if (mode == "w") return run_writers(MD, fout, u, du, states_path);
     double t = MD->CS.StartTime;
     std::vector<double> tmp((size_t)NE);
     for (int s = 0; s < n_et; s++) {

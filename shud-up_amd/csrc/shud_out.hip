@@ -117,7 +117,10 @@ __global__ void __launch_bounds__(256) k_snap_nc_sel(double *__restrict__ buf, d
 }
 
 // Model_Data::summary (MD_update.cpp:190-216): element storages and river stage from a state vector, BC
-// values where the element / reach has a head boundary condition
+// values where the element / reach has a head boundary condition.  summary(N_Vector) leaves yLakeStg alone: the
+// reference sets it in LoadIC and then in f_update only (MD_update.cpp:175), so ylake is given (non-null) only
+// before the handle's first evaluation, when the vector is the initial condition; afterwards
+// shud_rhs_refresh_diagnostics takes the lake entries of the last RHS input.
 __global__ void __launch_bounds__(256) k_summary(DevMesh m, const double *__restrict__ y, int ne, int nr, int nl,
                                                  double *ysf, double *yus, double *ygw, double *yriv, double *ylake) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -131,15 +134,19 @@ __global__ void __launch_bounds__(256) k_summary(DevMesh m, const double *__rest
         const int bc = m.riv_bc[i];
         yriv[i] = bc > 0 ? m.rybc[bc] : y[3 * ne + i];
     }
-    if (i < nl) ylake[i] = y[3 * ne + nr + i];                   // yLakeStg = Y[iLAKE] (MD_update.cpp:175)
+    if (ylake && i < nl) ylake[i] = y[3 * ne + nr + i];
 }
 
-// qEleTrans = Tg + Tu, qEleEvapo = Eu + Eg + Es (MD_ET.cpp:388-389), from the replayed diagnostics
-__global__ void __launch_bounds__(256) k_et_sums(DevDiag d, int ne, double *trans, double *evapo) {
+// qEleTrans = Tg + Tu, qEleEvapo = Eu + Eg + Es (MD_ET.cpp:388-389), from the replayed diagnostics; a lake
+// element has qEleTrans = 0 and qEleEvapo = qPotEvap (fun_Ele_lakeVertical, MD_ElementFlux.cpp:14-15).
+// lake_of: [ne] lake of a lake element, -1 otherwise; null for a model without lakes
+__global__ void __launch_bounds__(256) k_et_sums(DevDiag d, int ne, const int *__restrict__ lake_of,
+                                                 const double *__restrict__ pot_evap, double *trans, double *evapo) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ne) return;
-    trans[i] = d.q_tg[i] + d.q_tu[i];
-    evapo[i] = d.q_eu[i] + d.q_eg[i] + d.q_es[i];
+    const bool lake = lake_of && lake_of[i] >= 0;
+    trans[i] = lake ? 0. : d.q_tg[i] + d.q_tu[i];
+    evapo[i] = lake ? pot_evap[i] : d.q_eu[i] + d.q_eg[i] + d.q_es[i];
 }
 
 }  // namespace
@@ -607,7 +614,7 @@ extern "C" int shud_rhs_summary(shud_rhs_t h, const double *d_y) {
     const int n = std::max(ne, std::max(nr, nl));
     if (n > 0)
         hipLaunchKernelGGL(k_summary, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dm, d_y, ne, nr, nl,
-                           h->d_sum[0], h->d_sum[1], h->d_sum[2], h->d_sum[3], h->d_sum[4]);
+                           h->d_sum[0], h->d_sum[1], h->d_sum[2], h->d_sum[3], h->have_last ? nullptr : h->d_sum[4]);
     HIP_TRY(hipGetLastError());
     return SHUD_OK;
 }
@@ -619,9 +626,16 @@ extern "C" int shud_rhs_refresh_diagnostics(shud_rhs_t h) {
     const int ne = h->NE;
     if (!h->d_trans && ((rc = h->dalloc(&h->d_trans, ne)) || (rc = h->dalloc(&h->d_evapo, ne)))) return rc;
     if (ne > 0)
-        hipLaunchKernelGGL(k_et_sums, dim3((ne + 255) / 256), dim3(256), 0, h->stream, h->dd, ne, h->d_trans,
-                           h->d_evapo);
+        hipLaunchKernelGGL(k_et_sums, dim3((ne + 255) / 256), dim3(256), 0, h->stream, h->dd, ne,
+                           h->lakeon ? h->lk.lake_of : nullptr, h->dm.pot_evap, h->d_trans, h->d_evapo);
     HIP_TRY(hipGetLastError());
+    // yLakeStg = Y[iLAKE] of the last f() call (f_update, MD_update.cpp:175), like y2LakeArea (lake_toparea above):
+    // lakystage.dat and the restart file's lake block hold the last RHS input, not the vector given to summary
+    if (h->NL > 0) {
+        if (!h->d_sum[4] && (rc = h->dalloc(&h->d_sum[4], (size_t)h->NL))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_sum[4], h->last_y + 3 * (size_t)h->n_own + (size_t)h->n_own_riv,
+                               (size_t)h->NL * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
     return SHUD_OK;
 }
 

@@ -1,10 +1,25 @@
 """Pure-Python restatement of the reference's Print_Ctrl (test infrastructure: the checker of the device output
 path, include/shud_out.h).  Follows src/classes/Model_Control.cpp: Init/InitIJ (:759-858), open_file (:683-758),
 PrintData (:926-960), fun_printBINARY (:893-899), fun_printASCII (:900-909)."""
+import ctypes
+import ctypes.util
 import math
 import struct
 
 import numpy as np
+
+_LIBC = ctypes.CDLL(ctypes.util.find_library("c") or "libc.so.6")
+_LIBC.snprintf.restype = ctypes.c_int
+
+
+def _e(v):
+    """'%e' of glibc: Python's for a finite value; the sign and spelling of a non-finite one ('-nan') are glibc's"""
+    v = float(v)
+    if math.isfinite(v):
+        return f"{v:e}"
+    buf = ctypes.create_string_buffer(64)
+    _LIBC.snprintf(buf, ctypes.c_size_t(64), b"%e", ctypes.c_double(v))
+    return buf.value.decode()
 
 
 class PrintCtrlPy:
@@ -45,7 +60,7 @@ class PrintCtrlPy:
             self.num_update = 0
             tq = float(t_floor - self.interval)
             if self.fa:
-                self.fa.write(f"{tq:.1f}\t" + "".join(f"{v:e}\t" for v in self.buffer) + "\n")
+                self.fa.write(f"{tq:.1f}\t" + "".join(_e(v) + "\t" for v in self.buffer) + "\n")
             if self.fb:
                 self.fb.write(struct.pack("<d", tq))
                 self.fb.write(self.buffer.tobytes())

@@ -200,7 +200,29 @@ def sample_terms(m, ic_raw, d, prcp, stage):
     return {"P": prcp * area,
             "ET": (ic_raw + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * area,
             "Qout": outlet_terms(m, stage), "Qedge": edge if not m.close_boundary else np.zeros(0),
-            "Qbc": ele_qbc(m), "Qbc_riv": riv_qbc(m), "Qss": np.zeros(NE), "noncons": nc}
+            "Qbc": ele_qbc(m), "Qbc_riv": riv_qbc(m), "Qss": np.zeros(NE), "noncons": nc,
+            **edge_terms(m, qe, nb)}
+
+
+def edge_terms(m, qe, nb):
+    """the edge sums as the reference's loops add them: one term per edge in the order (element i, edge j), each
+    added to the running total on its own (:244-254, :483-488), not one value per element; 0.0 where an edge does
+    not count (adding it leaves the total as it is)"""
+    nc = np.where(nb >= 0, qe, 0.0).T.ravel()
+    edge = np.where(nb < 0, qe, 0.0).T.ravel() if not m.close_boundary else np.zeros(0)
+    return {"noncons_edges": nc, "Qedge_edges": edge}
+
+
+def basin_rates(tm, total, seq):
+    """the seven rates from the terms.  seq: the reference's association (every edge its own term; the reach
+    boundary fluxes go on adding to the element ones in one accumulator, :477-494); else one value per element
+    and two sums for Qbc, the device's"""
+    if seq:
+        return np.array([total(tm["P"]), total(tm["ET"]), total(tm["Qout"]), total(tm["Qedge_edges"]),
+                         total(np.concatenate([tm["Qbc"], tm["Qbc_riv"]])), total(tm["Qss"]),
+                         total(tm["noncons_edges"])])
+    return np.array([total(tm["P"]), total(tm["ET"]), total(tm["Qout"]), total(tm["Qedge"]),
+                     total(tm["Qbc"]) + total(tm["Qbc_riv"]), total(tm["Qss"]), total(tm["noncons"])])
 
 
 class WaterBalancePy:
@@ -209,6 +231,7 @@ class WaterBalancePy:
     def __init__(self, m, interval, state, start_time=0.0, trapz=False, prefix=None, order="device", **header):
         self.m, self.interval, self.trapz = m, int(interval), bool(trapz)
         self.sum = device_sum if order == "device" else seq_sum
+        self.seq = order != "device"
         NE = m.num_ele
         self.sy, self.area = m.par["Sy"], m.ele["area"]
         self.ic_raw = np.zeros(NE)
@@ -269,8 +292,7 @@ class WaterBalancePy:
             self.acc[k] = self._integrate(self.acc[k], self.prev[k], rate, dt)
             self.prev[k] = rate
         tm = sample_terms(m, ic, d, prcp, stage)
-        rate = np.array([self.sum(tm["P"]), self.sum(tm["ET"]), self.sum(tm["Qout"]), self.sum(tm["Qedge"]),
-                         self.sum(tm["Qbc"]) + self.sum(tm["Qbc_riv"]), self.sum(tm["Qss"]), self.sum(tm["noncons"])])
+        rate = basin_rates(tm, self.sum, self.seq)
         for k in range(7):
             self.basin_acc[k] = float(self._integrate(self.basin_acc[k], self.basin_prev[k], rate[k], dt))
         self.basin_prev = rate.copy()

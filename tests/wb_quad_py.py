@@ -32,15 +32,15 @@ def quad_terms(m, ic_raw, d, prcp):
     return {"P": prcp * area,
             "ET": (ic_raw + d["q_es"] + d["q_eu"] + d["q_eg"] + d["q_tu"] + d["q_tg"]) * area,
             "Qout": qout, "Qedge": edge if not m.close_boundary else np.zeros(0),
-            "Qbc": wb_py.ele_qbc(m), "Qbc_riv": wb_py.riv_qbc(m), "Qss": np.zeros(NE), "noncons": nc}
+            "Qbc": wb_py.ele_qbc(m), "Qbc_riv": wb_py.riv_qbc(m), "Qss": np.zeros(NE), "noncons": nc,
+            **wb_py.edge_terms(m, qe, nb)}
 
 
 def quad_rates(m, ic_raw, d, prcp, order="device"):
     """the seven rates [P, ET, Qout, Qedge, Qbc, Qss, noncons] in m3/min"""
     s = wb_py.device_sum if order == "device" else wb_py.seq_sum
     tm = quad_terms(m, ic_raw, d, prcp)
-    return np.array([s(tm["P"]), s(tm["ET"]), s(tm["Qout"]), s(tm["Qedge"]), s(tm["Qbc"]) + s(tm["Qbc_riv"]),
-                     s(tm["Qss"]), s(tm["noncons"])])
+    return wb_py.basin_rates(tm, s, order != "device")
 
 
 def quad_row(ds_total, acc):
