@@ -41,6 +41,10 @@ typedef struct {
 } ShudFloodSpec;
 /* FloodAlert::Init*: once per monitor set */
 int shud_mon_add_flood(shud_mon_t m, const ShudFloodSpec *s);
+/* on != 0, before shud_mon_add_flood: the flood file of an earlier run is kept (include/shud_ckpt.h) — opened
+ * without truncation, its header line compared, positioned at its end; shud_ckpt_restore then cuts it back to its
+ * length at the checkpoint and sets the row and snapshot counters. */
+int shud_mon_resume(shud_mon_t m, int on);
 /* FloodWarning(t) on the current contents of d_stage / d_qdown (stream-ordered): reach i gets a row iff
  * stage[i] > depth[i] (strict: a NaN stage gives no row, +inf does), rows in ascending i, calls in call order.
  * Returns after enqueue; waits only when both banks are still with the writer. */

@@ -111,6 +111,10 @@ typedef struct {
 int shud_out_create(int device, void *stream, shud_out_t *out);
 /* Print_Ctrl::Init[IJ] + open_file: creates/truncates the files and writes their headers */
 int shud_out_add(shud_out_t o, const ShudPrintSpec *spec);
+/* on != 0: controls added from now on keep the files of an earlier run (include/shud_ckpt.h) — opened without
+ * truncation, the header compared with the one shud_out_add writes (SHUD_ERR_ARG if it differs or the file is
+ * missing), positioned at the end; shud_ckpt_restore then cuts each file back to its length at the checkpoint. */
+int shud_out_resume(shud_out_t o, int on);
 /* shud_out_add over a source in another numbering (include/shud_order.h): column c of the file reads
  * d_src[col_src[c]], col_src host [n_all] with values in [0, n_all); flag_io and the header's column numbers are
  * still indexed by the caller's column c.  A create-time change: the export kernel already reads index lists. */

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "shud_ckpt_parts.h"
 #include "shud_et.h"
 #include "shud_out.h"
 #include "shud_et_dev.h"
@@ -273,6 +274,52 @@ extern "C" int shud_et_get(shud_rhs_t h, ShudEtOut *o) {
         shud_order_gather_host(h->inv.data(), h->NE, sizeof(double), 1, tmp.data(), x.dst);
     }
     return SHUD_OK;
+}
+
+// checkpoint access (shud_ckpt.cpp): the carried arrays — yEleIS / yEleSnow, the TSR factor cache, the cryosphere
+// sums and day-mean queues, the per-element forcing values and radiation terms of the last ET step (output controls
+// may point at them) — and the bookkeeping every element shares
+int shud_et_ckpt_dev(shud_rhs *h, CkptPart &p) {
+    if (!h || !h->et) return SHUD_OK;
+    const EtState *s = h->et;
+    const DevEt &e = s->e;
+    const size_t nb = (size_t)h->NE * sizeof(double);
+    const struct { const char *name; const double *ptr; } arr[] = {
+        {"et.y_is", e.y_is}, {"et.y_snow", e.y_snow}, {"et.tsr_factor", e.tsr_factor}, {"et.tacc_surf", e.tacc_surf},
+        {"et.tacc_sub", e.tacc_sub}, {"et.acc_surf", e.acc_surf}, {"et.acc_sub", e.acc_sub}, {"et.t_prcp", e.t_prcp},
+        {"et.t_temp", e.t_temp}, {"et.t_mf", e.t_mf}, {"et.t_rn", e.t_rn}, {"et.t_wind", e.t_wind}, {"et.t_rh", e.t_rh},
+        {"et.rn_factor", e.rn_factor}, {"et.rn_h", e.rn_h}, {"et.rn_t", e.rn_t}};
+    for (const auto &a : arr) p.add(a.name, a.ptr, nb);
+    if (s->par.cryosphere) {
+        p.add("et.ring_surf", e.ring_surf, (size_t)s->cap_surf * nb);
+        p.add("et.ring_sub", e.ring_sub, (size_t)s->cap_sub * nb);
+    }
+    return SHUD_OK;
+}
+int shud_et_ckpt_host(shud_rhs *h, CkptAr &a, bool check_only) {
+    EtState *s = h->et;
+    const ShudEtParams &q = s->par;      // field by field (the struct has padding)
+    const bool r[] = {a.same(q.cPrep), a.same(q.cTemp), a.same(q.cLAItsd), a.same(q.cMF), a.same(q.cETP), a.same(q.cISmax),
+                      a.same(q.radiation_input_mode), a.same(q.terrain_radiation), a.same(q.rad_factor_cap),
+                      a.same(q.rad_cosz_min), a.same(q.cryosphere), a.same(q.ft_surf_day), a.same(q.ft_sub_day),
+                      a.same(q.ft_surf_max), a.same(q.ft_surf_min), a.same(q.ft_sub_max), a.same(q.ft_sub_min)};
+    for (bool same : r)
+        if (!same) return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field ShudEtParams differs");
+    if (!a.same(s->cap_surf) || !a.same(s->cap_sub))
+        return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field ft_surf_day / ft_sub_day differs");
+    if (check_only) return SHUD_OK;
+    a.pod(s->tsr_ready);
+    return a.ok ? SHUD_OK : shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section et.host is too short");
+}
+// the cryosphere queue bookkeeping every element shares, a section of its own with a fixed layout
+// (csrc/shud_ckpt_parts.h)
+int shud_et_ckpt_queues(shud_rhs *h, CkptAr &a) {
+    EtState *s = h->et;
+    a.pod(s->head_surf); a.pod(s->size_surf); a.pod(s->head_sub); a.pod(s->size_sub); a.pod(s->n_of_day);
+    int32_t pad = 0;
+    a.pod(pad);
+    a.pod(s->time_start);
+    return a.ok ? SHUD_OK : shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section et.queues.host is too short");
 }
 
 const double *shud_et_array(shud_rhs *h, int which) {

@@ -18,6 +18,7 @@
 // reordered.  A failed copy means those rows / that snapshot are not written; the first failure is reported by
 // flush, destroy and the row getters.
 #include <hip/hip_runtime.h>
+#include <unistd.h>
 
 #include <cerrno>
 #include <chrono>
@@ -30,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "shud_ckpt_parts.h"
 #include "shud_diag_host.h"
 #include "shud_handle.h"
 #include "shud_mon.h"
@@ -189,6 +191,7 @@ struct shud_mon {
     double wsec = 0.0;
     int werr = 0;
     std::string werr_msg;
+    bool resume = false;                 // shud_mon_resume: add_flood keeps the file of an earlier run
 };
 
 static void mon_fail(shud_mon *m, int code, const std::string &msg) {
@@ -313,9 +316,17 @@ extern "C" int shud_mon_add_flood(shud_mon_t m, const ShudFloodSpec *s) {
     if (s->n_riv < 0 || (s->n_riv > 0 && (!s->d_stage || !s->d_qdown || !s->riv_depth || !s->riv_type)))
         return shud_fail(SHUD_ERR_ARG, "shud_mon_add_flood: bad n_riv or missing array");
     HIP_TRY(hipSetDevice(m->device));
-    FILE *fp = fopen(s->path, "w");                                  // InitFile
+    FILE *fp = fopen(s->path, m->resume ? "r+" : "w");               // InitFile
     if (!fp) return shud_fail(SHUD_MON_ERR_IO, "shud_mon_add_flood: cannot open %s: %s", s->path, strerror(errno));
-    if (fputs(shud_mon_flood_header(), fp) < 0 || fflush(fp) != 0) {
+    if (m->resume) {                     // shud_mon_resume: an earlier run's file, kept; its header must be ours
+        const std::string want = shud_mon_flood_header();
+        std::vector<char> have(want.size());
+        if (fread(have.data(), 1, have.size(), fp) != have.size() || memcmp(have.data(), want.data(), want.size()) != 0 ||
+            fseek(fp, 0, SEEK_END) != 0) {
+            fclose(fp);
+            return shud_fail(SHUD_ERR_ARG, "shud_mon_add_flood (resume): %s does not start with the flood header", s->path);
+        }
+    } else if (fputs(shud_mon_flood_header(), fp) < 0 || fflush(fp) != 0) {
         fclose(fp);
         return shud_fail(SHUD_MON_ERR_IO, "shud_mon_add_flood: cannot write %s", s->path);
     }
@@ -475,6 +486,34 @@ extern "C" int shud_mon_flush(shud_mon_t m) {
     if (!m) return shud_fail(SHUD_ERR_ARG, "null argument");
     mon_drain(m);
     return mon_report(m);
+}
+
+extern "C" int shud_mon_resume(shud_mon_t m, int on) {
+    if (!m) return shud_fail(SHUD_ERR_ARG, "null argument");
+    m->resume = on != 0;
+    return SHUD_OK;
+}
+
+// checkpoint access (shud_ckpt.cpp): the flood file's length with its row counters, and the snapshot counter;
+// loading cuts the flood file back to that length
+int shud_mon_ckpt_host(shud_mon *m, CkptAr &a, bool check_only) {
+    if (mon_drain(m)) return mon_report(m);
+    int hf = m->have_flood ? 1 : 0, hi = m->have_ic ? 1 : 0;
+    if (!a.same(hf) || !a.same(hi) || !a.same(m->nr))
+        return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field monitors (flood / snapshots / reaches) differs");
+    int64_t rows = m->rows, snaps = m->snaps;
+    int last = m->last;
+    long long len = (!a.load && m->ff) ? (long long)ftello(m->ff) : -1;
+    a.pod(rows); a.pod(snaps); a.pod(last); a.pod(len);
+    if (!a.ok) return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section mon.host is too short");
+    if (!a.load) return SHUD_OK;
+    if (m->ff && (fseeko(m->ff, 0, SEEK_END) != 0 || ftello(m->ff) < len))
+        return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: %s is shorter than at the checkpoint", m->fpath.c_str());
+    if (check_only) return SHUD_OK;
+    if (m->ff && (fflush(m->ff) != 0 || ftruncate(fileno(m->ff), len) != 0 || fseeko(m->ff, len, SEEK_SET) != 0))
+        return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: cannot cut %s back", m->fpath.c_str());
+    m->rows = rows; m->snaps = snaps; m->last = last;
+    return SHUD_OK;
 }
 
 extern "C" double shud_mon_writer_seconds(shud_mon_t m) {

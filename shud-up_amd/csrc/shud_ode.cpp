@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "shud_ckpt_parts.h"
 #include "shud_handle.h"
 #include "shud_ode.h"
 #include "shud_ode_dev.h"
@@ -1004,4 +1005,75 @@ extern "C" int shud_ode_destroy(shud_ode_t o) {
     (void)hipStreamSynchronize(o->s);
     ode_free(o);
     return SHUD_ODE_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------------
+// checkpoint access (shud_ckpt.cpp; csrc/shud_ckpt_parts.h)
+// ---------------------------------------------------------------------------------------------
+// the integrator's options and build settings: recorded by a snapshot, compared by a restore
+int shud_ode_ckpt_check(shud_ode *o, ShudCkptInfo *hdr, bool restore) {
+    if (!o || !hdr) return shud_fail(SHUD_ERR_ARG, "shud_ckpt: null integrator");
+    if (o->rhs_failed || o->hip_failed) return shud_fail(SHUD_ERR_ARG, "shud_ckpt: the integrator has failed");
+    if (!restore) {
+        hdr->ny = o->n;
+        hdr->ode_reltol = o->rtol; hdr->ode_abstol = o->atol; hdr->ode_init_step = o->hin; hdr->ode_min_step = o->hmin;
+        hdr->ode_max_step_inv = o->hmax_inv; hdr->ode_max_num_steps = o->mxstep; hdr->ode_maxl = o->maxl;
+        hdr->ode_max_order = o->qmax; hdr->ode_lazy = ode::lazy_ycor();
+        return SHUD_OK;
+    }
+    auto bad = [](const char *f) { return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: integrator field %s differs", f); };
+    if (hdr->ny != o->n) return bad("ny");
+    if (memcmp(&hdr->ode_reltol, &o->rtol, 8)) return bad("reltol");
+    if (memcmp(&hdr->ode_abstol, &o->atol, 8)) return bad("abstol");
+    if (memcmp(&hdr->ode_init_step, &o->hin, 8)) return bad("init_step");
+    if (memcmp(&hdr->ode_min_step, &o->hmin, 8)) return bad("min_step");
+    if (memcmp(&hdr->ode_max_step_inv, &o->hmax_inv, 8)) return bad("max_step");
+    if (hdr->ode_max_num_steps != o->mxstep) return bad("max_num_steps");
+    if (hdr->ode_maxl != o->maxl) return bad("maxl");
+    if (hdr->ode_max_order != o->qmax) return bad("max_order");
+    if (hdr->ode_lazy != ode::lazy_ycor()) return bad("SHUD_ODE_LAZY_YCOR");
+    return SHUD_OK;
+}
+
+// the device vectors that are live between two solves: the Nordsieck columns, acor (the deferred completion reads
+// it), both error-weight vectors, y / ftemp / tempv (a replay or a host read may look at them), the scalar slots.
+// delta, work and the Krylov basis are written before they are read in every step.
+int shud_ode_ckpt_dev(shud_ode *o, CkptPart &p) {
+    HIP_TRY(hipSetDevice(o->device));
+    HIP_TRY(hipStreamSynchronize(o->s));                 // nothing in flight (no fetch: n_sync stays the run's own)
+    const size_t nb = (size_t)o->n * sizeof(double);
+    p.add("ode.zn", o->zn, (size_t)(o->qmax + 1) * nb);
+    p.add("ode.acor", o->acor, nb);
+    p.add("ode.ewt", o->ewt, nb);
+    p.add("ode.ewt_alt", o->ewt_alt, nb);
+    p.add("ode.y", o->y, nb);
+    p.add("ode.ftemp", o->ftemp, nb);
+    p.add("ode.tempv", o->tempv, nb);
+    p.add("ode.ds", o->d_ds, S_COUNT * sizeof(double));
+    return SHUD_OK;
+}
+
+void *shud_ode_ckpt_stream(shud_ode *o) { return (void *)o->s; }
+
+int shud_ode_ckpt_host(shud_ode *o, CkptAr &a) {
+    a.pod(o->tn); a.pod(o->h); a.pod(o->hprime); a.pod(o->next_h); a.pod(o->eta); a.pod(o->etamax); a.pod(o->hscale);
+    a.pod(o->h0u); a.pod(o->hu); a.pod(o->tau); a.pod(o->tq); a.pod(o->l);
+    a.pod(o->rl1); a.pod(o->gamma); a.pod(o->gammap); a.pod(o->gamrat); a.pod(o->crate); a.pod(o->delp); a.pod(o->acnrm);
+    a.pod(o->saved_tq5); a.pod(o->tstop); a.pod(o->tretlast); a.pod(o->tolsf); a.pod(o->etaq); a.pod(o->etaqm1);
+    a.pod(o->etaqp1); a.pod(o->nrmfac);
+    a.pod(o->acor_zero); a.pod(o->acor_lazy); a.pod(o->y_pred); a.pod(o->ewt_pending);
+    a.pod(o->tstopset); a.pod(o->q); a.pod(o->qprime); a.pod(o->next_q); a.pod(o->qwait); a.pod(o->L); a.pod(o->qu);
+    a.pod(o->indx_acor); a.pod(o->convfail); a.pod(o->jcur); a.pod(o->jbad); a.pod(o->curiter); a.pod(o->initialized);
+    a.pod(o->nst); a.pod(o->nscon); a.pod(o->nstlp); a.pod(o->nfe); a.pod(o->nfeDQ); a.pod(o->nni); a.pod(o->nnf);
+    a.pod(o->ncfn); a.pod(o->netf); a.pod(o->nsetups); a.pod(o->nli); a.pod(o->ncfl); a.pod(o->njtimes); a.pod(o->nhnil);
+    a.pod(o->n_sync); a.pod(o->ewt_fin_sync); a.pod(o->fin_seq);
+    a.pod(o->Hes); a.pod(o->gv); a.pod(o->yg);
+    // the deferred completion: its pointer is stored as "acor or none" (it never points anywhere else)
+    int pend_on = o->pend.acor ? 1 : 0;
+    a.pod(pend_on);
+    a.pod(o->pend.l); a.pod(o->pend.r); a.pod(o->pend.q); a.pod(o->pend.copy_to); a.pod(o->pend.resc); a.pod(o->pend.j0);
+    if (a.load) o->pend.acor = pend_on ? o->acor : nullptr;
+    // the host-mapped twin of the scalar slots, with the last finalize's sequence number (fetch polls it)
+    a.raw(o->h_ds, (S_COUNT + 2) * sizeof(double));
+    return a.ok ? SHUD_OK : shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section ode.host is too short");
 }

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <cmath>
 #include <condition_variable>
@@ -35,6 +36,7 @@
 #include <thread>
 #include <vector>
 
+#include "shud_ckpt_parts.h"
 #include "shud_diag_host.h"
 #include "shud_handle.h"
 #include "shud_nc.h"
@@ -203,6 +205,7 @@ struct shud_out {
     std::string werr_msg;
     shud_nc_t nc[SHUD_NC_KINDS] = {nullptr, nullptr, nullptr};   // attached NetCDF files
     bool nc_begun = false;
+    bool resume = false;                 // shud_out_resume: controls added from now on keep their files
 };
 static void writer_fail(shud_out *o, int code, const std::string &msg) {
     std::lock_guard<std::mutex> lk(o->mu);
@@ -353,28 +356,66 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src,
     }
     // open_file: fixed 1024-byte header, StartTime, NumVar, icol (binary); the ASCII twin's preamble
     const char *mode = s->solar_lonlat_mode ? s->solar_lonlat_mode : "";
-    if (legacy && s->binary) {
-        const std::string fb = p.filename + ".dat";
-        p.fb = fopen(fb.c_str(), "wb");
-        if (!p.fb) return out_fail_io("shud_out_add", fb);
+    auto dat_preamble = [&](FILE *fp) {
         // a failed write here is not reported; every row's write is checked (writer_loop)
-        (void)shud::write_dat_preamble(p.fb, nullptr, s->radiation_input_mode, s->terrain_radiation, mode,
+        (void)shud::write_dat_preamble(fp, nullptr, s->radiation_input_mode, s->terrain_radiation, mode,
                                        s->solar_lon_deg, s->solar_lat_deg, (double)p.start_time, p.numvar,
                                        p.icol.data());
+    };
+    auto csv_preamble = [&](FILE *fp) {
+        fprintf(fp, "# Timestamp semantics: left endpoint (t-Interval)\n");
+        fprintf(fp, "%d\t %d\t %ld\n", 0, p.numvar, (long)p.start_time);
+        fprintf(fp, "# Radiation input mode: %s\n", s->radiation_input_mode == 1 ? "SWNET" : "SWDOWN");
+        fprintf(fp, "# Terrain radiation (TSR): %s\n", s->terrain_radiation ? "ON" : "OFF");
+        fprintf(fp, "# Solar lon/lat mode: %s\n", mode);
+        fprintf(fp, "# Solar lon/lat (deg): lon=%.6f, lat=%.6f\n", s->solar_lon_deg, s->solar_lat_deg);
+        fprintf(fp, "%s", "Time_min");
+        for (int i = 0; i < p.numvar; i++) fprintf(fp, " \tX%d", i + 1);
+        fprintf(fp, "\n");
+    };
+    // shud_out_resume: the file of an earlier run is kept — opened without truncation, its preamble compared with
+    // the one written above, positioned at its end (shud_ckpt_restore cuts it back to the checkpoint's length)
+    auto reopen = [&](const std::string &f, auto &preamble, FILE **out) -> int {
+        char *want = nullptr;
+        size_t nwant = 0;
+        FILE *ms = open_memstream(&want, &nwant);
+        if (!ms) return out_fail_io("shud_out_add", f);
+        preamble(ms);
+        fclose(ms);
+        FILE *fp = fopen(f.c_str(), "r+b");
+        std::vector<char> have(nwant);
+        const bool same = fp && fread(have.data(), 1, nwant, fp) == nwant && memcmp(have.data(), want, nwant) == 0;
+        free(want);
+        if (!fp) return out_fail_io("shud_out_add (resume)", f);
+        if (!same || fseek(fp, 0, SEEK_END) != 0) {
+            fclose(fp);
+            return shud_fail(SHUD_ERR_ARG, "shud_out_add (resume): the header of %s is not the one this control writes",
+                             f.c_str());
+        }
+        *out = fp;
+        return SHUD_OK;
+    };
+    if (legacy && s->binary) {
+        const std::string fb = p.filename + ".dat";
+        if (o->resume) {
+            const int rc = reopen(fb, dat_preamble, &p.fb);
+            if (rc) return rc;
+        } else {
+            p.fb = fopen(fb.c_str(), "wb");
+            if (!p.fb) return out_fail_io("shud_out_add", fb);
+            dat_preamble(p.fb);
+        }
     }
     if (legacy && s->ascii) {
         const std::string fa = p.filename + ".csv";
-        p.fa = fopen(fa.c_str(), "w");
-        if (!p.fa) return out_fail_io("shud_out_add", fa);
-        fprintf(p.fa, "# Timestamp semantics: left endpoint (t-Interval)\n");
-        fprintf(p.fa, "%d\t %d\t %ld\n", 0, p.numvar, (long)p.start_time);
-        fprintf(p.fa, "# Radiation input mode: %s\n", s->radiation_input_mode == 1 ? "SWNET" : "SWDOWN");
-        fprintf(p.fa, "# Terrain radiation (TSR): %s\n", s->terrain_radiation ? "ON" : "OFF");
-        fprintf(p.fa, "# Solar lon/lat mode: %s\n", mode);
-        fprintf(p.fa, "# Solar lon/lat (deg): lon=%.6f, lat=%.6f\n", s->solar_lon_deg, s->solar_lat_deg);
-        fprintf(p.fa, "%s", "Time_min");
-        for (int i = 0; i < p.numvar; i++) fprintf(p.fa, " \tX%d", i + 1);
-        fprintf(p.fa, "\n");
+        if (o->resume) {
+            const int rc = reopen(fa, csv_preamble, &p.fa);
+            if (rc) return rc;
+        } else {
+            p.fa = fopen(fa.c_str(), "w");
+            if (!p.fa) return out_fail_io("shud_out_add", fa);
+            csv_preamble(p.fa);
+        }
     }
     o->max_nvar = std::max(o->max_nvar, p.numvar);
     o->slots.push_back(PrintSlot{s->d_src, p.d_sel, p.d_buf, p.numvar});
@@ -535,6 +576,76 @@ extern "C" int shud_out_flush(shud_out_t o) {
     if (!o) return shud_fail(SHUD_ERR_ARG, "null argument");
     out_drain(o);
     return out_report(o);
+}
+
+extern "C" int shud_out_resume(shud_out_t o, int on) {
+    if (!o) return shud_fail(SHUD_ERR_ARG, "null argument");
+    o->resume = on != 0;
+    return SHUD_OK;
+}
+
+// ---- checkpoint access (shud_ckpt.cpp) ----
+int shud_out_ckpt_check(shud_out *o) {
+    for (int k = 0; k < SHUD_NC_KINDS; k++)
+        if (o->nc[k])
+            return shud_fail(SHUD_ERR_UNSUPPORTED, "shud_ckpt: an output set with a NetCDF sink cannot be checkpointed "
+                                                   "(a record file has no reopen path)");
+    return SHUD_OK;
+}
+void *shud_out_ckpt_stream(shud_out *o) { return (void *)o->stream; }
+// each control's accumulator, once every queued row is in its file
+int shud_out_ckpt_dev(shud_out *o, CkptPart &p) {
+    HIP_TRY(hipSetDevice(o->device));
+    if (out_drain(o)) return out_report(o);
+    HIP_TRY(hipStreamSynchronize(o->stream));            // the last export's accumulate pass
+    for (size_t k = 0; k < o->pc.size(); k++) {
+        char name[SHUD_CKPT_NAME_LEN];
+        snprintf(name, sizeof(name), "out.buf%zu", k);
+        p.add(name, o->pc[k].d_buf, ((size_t)std::max(o->pc[k].numvar, 1) + 3) / 4 * 4 * sizeof(double));
+    }
+    return SHUD_OK;
+}
+// interval bookkeeping, rows and the byte length of each file; loading cuts every file back to that length
+int shud_out_ckpt_host(shud_out *o, CkptAr &a, bool check_only) {
+    int n = (int)o->pc.size();
+    if (!a.same(n)) return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field number of output controls differs");
+    std::vector<long long> len(2 * (size_t)n, -1);
+    for (int k = 0; k < n; k++) {
+        PrintCtrl &p = o->pc[k];
+        int has_b = p.fb ? 1 : 0, has_a = p.fa ? 1 : 0;
+        if (!a.same(p.numvar) || !a.same(p.interval) || !a.same(p.start_time) || !a.same(has_b) || !a.same(has_a))
+            return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: output control %d (%s) differs", k, p.filename.c_str());
+        int nu = p.num_update;
+        int64_t rows = p.rows;
+        FILE *fp[2] = {p.fb, p.fa};
+        a.pod(nu);
+        a.pod(rows);
+        for (int j = 0; j < 2; j++) {
+            long long l = -1;
+            if (!a.load && fp[j]) l = ftello(fp[j]);
+            a.pod(l);
+            len[2 * k + j] = l;
+            if (a.load && fp[j]) {                   // the file must still hold everything up to the checkpoint
+                if (fseeko(fp[j], 0, SEEK_END) != 0 || ftello(fp[j]) < l)
+                    return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: %s%s is shorter than at the checkpoint",
+                                     p.filename.c_str(), j ? ".csv" : ".dat");
+            }
+        }
+        if (a.load && !check_only) {
+            p.num_update = nu;
+            p.rows = rows;
+        }
+    }
+    if (!a.ok) return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section out.host is too short");
+    if (a.load && !check_only)
+        for (int k = 0; k < n; k++) {
+            FILE *fp[2] = {o->pc[k].fb, o->pc[k].fa};
+            for (int j = 0; j < 2; j++)
+                if (fp[j] && (fflush(fp[j]) != 0 || ftruncate(fileno(fp[j]), len[2 * k + j]) != 0 ||
+                              fseeko(fp[j], len[2 * k + j], SEEK_SET) != 0))
+                    return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: cannot cut %s back", o->pc[k].filename.c_str());
+        }
+    return SHUD_OK;
 }
 
 extern "C" int64_t shud_out_rows(shud_out_t o, int k) {

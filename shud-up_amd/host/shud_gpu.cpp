@@ -2,7 +2,7 @@
 // prelude, the integrator and the outputs on one MI355X, driven through the C-ABIs of include/.
 //
 //   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] [--reorder bfs|tiles]
-//            <input_dir> <project>
+//            [--checkpoint PATH [--checkpoint-every N]] [--resume PATH] <input_dir> <project>
 //   shud_gpu --rhs-check K | --rhs-bench [--evals N] ...   partitioned RHS modes (shud_gpu_part.cpp)
 //
 // input_dir/<project>.* are the reference's input files (FileIn, IO.cpp:53-91); forcing csv paths in
@@ -66,6 +66,7 @@
 
 #include "shud_et.h"
 #include "shud_host.h"
+#include "shud_ckpt.h"
 #include "shud_mon.h"
 #include "shud_ode.h"
 #include "shud_order.h"
@@ -77,12 +78,18 @@ static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 
 static void usage() {
     fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots]\n"
-                    "                [--reorder bfs|tiles] <input_dir> <project>\n"
+                    "                [--reorder bfs|tiles] [--checkpoint PATH [--checkpoint-every N]] [--resume PATH]\n"
+                    "                <input_dir> <project>\n"
                     "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n"
                     "  --flood         write <outdir>/<project>.flood.csv (reaches above their bank after each solver step)\n"
                     "  --ic-snapshots  write <outdir>/<project>.cfg.ic.bak and, every Update_IC_STEP minutes and at the\n"
                     "                  end, <outdir>/<project>.cfg.ic.update (restart file for INIT_MODE 3)\n"
                     "  Both are off by default (the reference always writes these files).\n"
+                    "  --checkpoint PATH  write an exact checkpoint of the device run to PATH at the end of the run and,\n"
+                    "                  with --checkpoint-every N, after every N solver steps (the run goes on while it drains)\n"
+                    "  --resume PATH   continue from a checkpoint into the same outdir: -n and -e count from the original\n"
+                    "                  start, the files are cut back to the checkpoint and end up those of one straight run.\n"
+                    "                  Neither with SHUD_WB_DIAG nor with OUTPUT_MODE NETCDF | BOTH.\n"
                     "  --reorder ORDER run the device side in a planned element order (neighbours close in memory);\n"
                     "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n"
                     "                  tiles: breadth-first pockets that each fill one 256-element sharing tile;\n"
@@ -138,7 +145,8 @@ int main(int argc, char **argv) {
     bool quiet = false;
     int rhs_check = 0, evals = 0;
     bool rhs_bench = false, want_flood = false, want_ic = false;
-    std::string reorder;
+    std::string reorder, ckpt_path, resume_path;
+    long long ckpt_every = 0;
     std::vector<const char *> pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -153,6 +161,9 @@ int main(int argc, char **argv) {
         else if (a == "--ic-snapshots") want_ic = true;
         else if (a == "--reorder" && i + 1 < argc) reorder = argv[++i];
         else if (a == "--evals" && i + 1 < argc) evals = atoi(argv[++i]);
+        else if (a == "--checkpoint" && i + 1 < argc) ckpt_path = argv[++i];
+        else if (a == "--checkpoint-every" && i + 1 < argc) ckpt_every = atoll(argv[++i]);
+        else if (a == "--resume" && i + 1 < argc) resume_path = argv[++i];
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else pos.push_back(argv[i]);
     }
@@ -166,6 +177,16 @@ int main(int argc, char **argv) {
     if (!reorder.empty() && env_truthy(getenv("SHUD_WB_DIAG"))) {
         fprintf(stderr, "--reorder cannot be combined with SHUD_WB_DIAG: the water-balance sums over the basin would "
                         "run in another element order\n");
+        return 1;
+    }
+    const bool want_ckpt = !ckpt_path.empty() || !resume_path.empty();
+    if (ckpt_every < 0 || (ckpt_every > 0 && ckpt_path.empty())) {
+        fprintf(stderr, "--checkpoint-every N needs N >= 1 and --checkpoint PATH\n");
+        return 1;
+    }
+    if (want_ckpt && env_truthy(getenv("SHUD_WB_DIAG"))) {
+        fprintf(stderr, "--checkpoint / --resume cannot be combined with SHUD_WB_DIAG: the water-balance object keeps "
+                        "accumulators of its own, which a checkpoint does not hold\n");
         return 1;
     }
     const auto wall0 = std::chrono::steady_clock::now();
@@ -292,6 +313,13 @@ int main(int argc, char **argv) {
     shud_project_ncoutput(p, &ncc);
     static const char *mode_name[3] = {"LEGACY", "NETCDF", "BOTH"};
     if (!quiet) printf("* \t OUTPUT_MODE: %s\n", mode_name[ncc.output_mode]);      // Model_Control.cpp:641-643
+    if (want_ckpt && ncc.output_mode != 0) {
+        fprintf(stderr, "--checkpoint / --resume cannot be combined with OUTPUT_MODE %s: a NetCDF record file has no "
+                        "reopen path, so a resumed run could not continue it\n", mode_name[ncc.output_mode]);
+        return 1;
+    }
+    // --resume: the controls keep the files of the run that wrote the checkpoint (cut back at the restore below)
+    if (!resume_path.empty()) shud_out_resume(out, 1);
     if (ncc.output_mode != 0) {
         int64_t nnode = 0;
         const double *node_x = shud_project_node_xy(p, 0, &nnode), *node_y = shud_project_node_xy(p, 1, nullptr);
@@ -390,6 +418,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "shud_mon_create: %s\n", shud_rhs_last_error_string());
             return 1;
         }
+        if (!resume_path.empty()) shud_mon_resume(mon, 1);
         if (want_ic) {
             const std::string bak = outdir + "/" + prj + ".cfg.ic.bak";
             if (ic_from_host(bak, 0)) {
@@ -452,6 +481,31 @@ int main(int argc, char **argv) {
     double t = c.start_time, tnext = t;
     const long long nsteps = max_steps >= 0 && max_steps < c.num_steps ? max_steps : c.num_steps;
     int rc = 0;
+    // ---- --checkpoint / --resume (include/shud_ckpt.h): the loop index, -n and -e count from the original start ----
+    shud_ckpt_t ckpt = nullptr;
+    const ShudCkptParts parts = {h, ode, out, mon, wb};
+    long long i0 = 0;
+    if (!resume_path.empty()) {
+        int64_t step = 0;
+        if (shud_ckpt_restore(resume_path.c_str(), &parts, &t, &step)) {
+            fprintf(stderr, "--resume %s: %s\n", resume_path.c_str(), shud_rhs_last_error_string());
+            return 1;
+        }
+        i0 = (long long)step;
+        tnext = t;
+        if (!quiet) printf("* \t resumed from %s: solver step %lld, t = %.3f min\n", resume_path.c_str(), i0, t);
+    }
+    if (!ckpt_path.empty() && shud_ckpt_create(0, shud_rhs_stream(h), &ckpt)) {
+        fprintf(stderr, "shud_ckpt_create: %s\n", shud_rhs_last_error_string());
+        return 1;
+    }
+    auto checkpoint = [&](long long step) {
+        if (shud_ckpt_snapshot(ckpt, &parts, t, step, ckpt_path.c_str())) {
+            fprintf(stderr, "--checkpoint %s: %s\n", ckpt_path.c_str(), shud_rhs_last_error_string());
+            return 1;
+        }
+        return 0;
+    };
     // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
     // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag, quad monitor (its f(), replay and pass)
     // run monitors (their enqueue; the writer thread's own time is reported beside it)
@@ -462,7 +516,7 @@ int main(int argc, char **argv) {
         ph[k] += std::chrono::duration<double>(now - tick).count();
         tick = now;
     };
-    for (long long i = 0; i < nsteps && !rc; i++) {
+    for (long long i = i0; i < nsteps && !rc; i++) {
         if (want_ic) {                            // MD->PrintInit(fout->Init_update, t)
             if (ic_update_at(t, i > 0)) {
                 rc = 1;
@@ -574,9 +628,18 @@ int main(int argc, char **argv) {
             lap(7);
         }
         if (!quiet && c.verbose) printf("step %lld  t = %.3f min\n", i + 1, t);
+        // stepping goes on while the checkpoint drains; the one after the last step is written below
+        if (ckpt && !rc && ckpt_every > 0 && (i + 1) % ckpt_every == 0 && i + 1 < nsteps) rc = checkpoint(i + 1);
+    }
+    if (ckpt) {                                   // the state at the end of the run: --resume continues from here
+        if (!rc && nsteps >= i0) rc = checkpoint(nsteps > i0 ? nsteps : i0);
+        if (shud_ckpt_destroy(ckpt)) {            // waits for the file
+            fprintf(stderr, "--checkpoint %s: %s\n", ckpt_path.c_str(), shud_rhs_last_error_string());
+            if (!rc) rc = 1;
+        }
     }
     if (want_ic && !rc) {                         // MD->PrintInit(fout->Init_update, t) after the loop
-        if (ic_update_at(t, nsteps > 0)) rc = 1;
+        if (ic_update_at(t, nsteps > 0 || i0 > 0)) rc = 1;
         lap(7);
     }
     shud_rhs_synchronize(h);

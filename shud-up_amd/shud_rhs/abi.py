@@ -373,12 +373,66 @@ ORDER_FUNCTIONS = {
 }
 
 
+# ---- include/shud_ckpt.h (exact checkpoint / resume of a device run) ----
+SHUD_CKPT_MAGIC = b"SHUDCKP1"
+SHUD_CKPT_VERSION = 1
+SHUD_CKPT_NAME_LEN = 24
+SHUD_CKPT_LAYOUT_SOA, SHUD_CKPT_LAYOUT_PACKED, SHUD_CKPT_LAYOUT_HYBRID = 0, 1, 2
+
+
+class ShudCkptInfo(C.Structure):
+    _fields_ = ([("magic", C.c_char * 8), ("version", C.c_uint32), ("abi_version", C.c_uint32),
+                 ("n_sections", C.c_uint32), ("header_bytes", C.c_uint32)] +
+                [(n, C.c_int32) for n in ("ne", "nr", "ns", "nl")] + [("ny", C.c_int64)] +
+                [(n, C.c_int32) for n in ("mode", "layout", "n_classes", "n_streamed", "n_shared", "order_kind",
+                                          "have_rhs", "have_et", "have_ode", "have_out", "have_mon", "ode_lazy")] +
+                [(n, C.c_uint64) for n in ("perm_c0", "perm_c1", "statics_c0", "statics_c1")] +
+                [(n, C.c_double) for n in ("ode_reltol", "ode_abstol", "ode_init_step", "ode_min_step",
+                                           "ode_max_step_inv")] +
+                [("ode_max_num_steps", C.c_int64), ("ode_maxl", C.c_int32), ("ode_max_order", C.c_int32),
+                 ("t", C.c_double), ("step", C.c_int64), ("payload_words", C.c_uint64), ("hdr_c0", C.c_uint64),
+                 ("hdr_c1", C.c_uint64)])
+
+
+class ShudCkptSection(C.Structure):
+    _fields_ = [("name", C.c_char * SHUD_CKPT_NAME_LEN), ("offset", C.c_uint64), ("words", C.c_uint64),
+                ("c0", C.c_uint64), ("c1", C.c_uint64)]
+
+
+class ShudCkptParts(C.Structure):
+    _fields_ = [("rhs", C.c_void_p), ("ode", C.c_void_p), ("out", C.c_void_p), ("mon", C.c_void_p),
+                ("wb", C.c_void_p)]
+
+
+c_uint64_p = C.POINTER(C.c_uint64)
+c_int64_p = C.POINTER(C.c_int64)
+CKPT_FUNCTIONS = {
+    "shud_ckpt_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(_H)]),
+    "shud_ckpt_snapshot": (C.c_int, [_H, C.POINTER(ShudCkptParts), C.c_double, C.c_int64, C.c_char_p]),
+    "shud_ckpt_flush": (C.c_int, [_H]),
+    "shud_ckpt_destroy": (C.c_int, [_H]),
+    "shud_ckpt_info": (C.c_int, [C.c_char_p, C.POINTER(ShudCkptInfo)]),
+    "shud_ckpt_section": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(ShudCkptSection)]),
+    "shud_ckpt_verify": (C.c_int, [C.c_char_p]),
+    "shud_ckpt_restore": (C.c_int, [C.c_char_p, C.POINTER(ShudCkptParts), c_double_p, c_int64_p]),
+    "shud_ckpt_checksum": (None, [c_uint64_p, C.c_uint64, c_uint64_p, c_uint64_p]),
+    "shud_ckpt_write_sections": (C.c_int, [C.c_char_p, C.POINTER(ShudCkptInfo), C.c_int32, C.POINTER(C.c_char_p),
+                                           C.POINTER(C.c_void_p), c_uint64_p]),
+    "shud_ckpt_read_section": (C.c_int, [C.c_char_p, C.c_char_p, c_uint64_p, C.c_uint64, c_uint64_p]),
+    "shud_ckpt_pack_test": (C.c_int, [C.c_int32, c_uint64_p, c_int64_p, c_int32_p, C.c_int32, C.c_uint64, C.c_int32,
+                                      c_uint64_p, C.c_int64, c_int64_p, c_int64_p, c_uint64_p, c_uint64_p]),
+    "shud_ckpt_time_pack": (C.c_int, [_H, C.POINTER(ShudCkptParts), C.c_int, c_double_p, c_int64_p]),
+}
+OUT_FUNCTIONS["shud_out_resume"] = (C.c_int, [_H, C.c_int])
+MON_FUNCTIONS["shud_mon_resume"] = (C.c_int, [_H, C.c_int])
+
+
 def bind(lib, strict=True):
     """set the signatures; strict=False (A/B builds of older sources) skips symbols the library lacks"""
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
                               + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())
                               + list(MON_FUNCTIONS.items()) + list(ORDER_FUNCTIONS.items())
-                              + list(NC_FUNCTIONS.items())):
+                              + list(NC_FUNCTIONS.items()) + list(CKPT_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

@@ -504,6 +504,11 @@ class Output:
         _check(lib().shud_out_time_nc(self.h, int(k), int(reps), C.byref(ms)), "shud_out_time_nc")
         return ms.value
 
+    def resume(self, on=True):
+        """controls added from now on keep the files of an earlier run (shud_out_resume; Checkpoint.restore then cuts
+        them back to the checkpoint's length)"""
+        _check(lib().shud_out_resume(self.h, int(bool(on))), "shud_out_resume")
+
     def export(self, t):
         _check(lib().shud_out_export(self.h, float(t)), "shud_out_export")
 
@@ -725,6 +730,10 @@ class RunMonitors:
         self._keep.append((pth, d_stage, d_qdown))
         _check(lib().shud_mon_add_flood(self.h, C.byref(spec)), "shud_mon_add_flood")
 
+    def resume(self, on=True):
+        """add_flood keeps the flood file of an earlier run (shud_mon_resume)"""
+        _check(lib().shud_mon_resume(self.h, int(bool(on))), "shud_mon_resume")
+
     def flood(self, t):
         _check(lib().shud_mon_flood(self.h, float(t)), "shud_mon_flood")
 
@@ -788,6 +797,83 @@ class RunMonitors:
             rc = lib().shud_mon_destroy(self.h)
             self.h = None
             _check(rc, "shud_mon_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def _ckpt_parts(rhs=None, ode=None, output=None, monitors=None, wb=None):
+    def raw(x):
+        return None if x is None else x.h
+    return abi.ShudCkptParts(raw(rhs), raw(ode), raw(output), raw(monitors), raw(wb))
+
+
+class Checkpoint:
+    """Exact checkpoint / resume of a device run (include/shud_ckpt.h).  snapshot() is called between two solver
+    steps, after that step's export and monitors: one device pass packs the live state into a staging slab and the
+    call returns; the file is written in the background (flush).  restore() / info() / verify() need no object."""
+
+    def __init__(self, device=0, stream=None):
+        h = C.c_void_p()
+        _check(lib().shud_ckpt_create(int(device), None if stream is None else C.c_void_p(stream), C.byref(h)),
+               "shud_ckpt_create")
+        self.h = h
+
+    def snapshot(self, path, t, step, ode, rhs=None, output=None, monitors=None, wb=None):
+        """wb: the run's WaterBalance, if any — the checkpoint is then refused (SHUD_ERR_UNSUPPORTED)"""
+        parts = _ckpt_parts(rhs, ode, output, monitors, wb)
+        _check(lib().shud_ckpt_snapshot(self.h, C.byref(parts), float(t), int(step), str(path).encode()),
+               "shud_ckpt_snapshot")
+
+    def flush(self):
+        """the last snapshot's file is complete and renamed into place; raises on the writer's first failure"""
+        _check(lib().shud_ckpt_flush(self.h), "shud_ckpt_flush")
+
+    def time_pack(self, reps, ode, rhs=None, output=None, monitors=None):
+        """(ms per pack pass, bytes it copies) over the live objects (shud_ckpt_time_pack)"""
+        parts = _ckpt_parts(rhs, ode, output, monitors)
+        ms, nb = C.c_double(), C.c_int64()
+        _check(lib().shud_ckpt_time_pack(self.h, C.byref(parts), int(reps), C.byref(ms), C.byref(nb)),
+               "shud_ckpt_time_pack")
+        return ms.value, nb.value
+
+    @staticmethod
+    def restore(path, ode, rhs=None, output=None, monitors=None):
+        """-> (t, solver-step index).  The objects are built as for a new run (output controls after
+        Output.resume(), the flood monitor after RunMonitors.resume()); a refused restore leaves them untouched."""
+        parts = _ckpt_parts(rhs, ode, output, monitors)
+        t, step = C.c_double(), C.c_int64()
+        _check(lib().shud_ckpt_restore(str(path).encode(), C.byref(parts), C.byref(t), C.byref(step)),
+               "shud_ckpt_restore")
+        return t.value, step.value
+
+    @staticmethod
+    def info(path):
+        """header fields (dict) and the section table [(name, offset, words, c0, c1)]"""
+        i = abi.ShudCkptInfo()
+        _check(lib().shud_ckpt_info(str(path).encode(), C.byref(i)), "shud_ckpt_info")
+        d = {k: getattr(i, k) for k, _ in abi.ShudCkptInfo._fields_}
+        secs = []
+        for k in range(i.n_sections):
+            s = abi.ShudCkptSection()
+            _check(lib().shud_ckpt_section(str(path).encode(), k, C.byref(s)), "shud_ckpt_section")
+            secs.append((s.name.decode(), s.offset, s.words, s.c0, s.c1))
+        d["sections"] = secs
+        return d
+
+    @staticmethod
+    def verify(path):
+        _check(lib().shud_ckpt_verify(str(path).encode()), "shud_ckpt_verify")
+
+    def close(self):
+        """shud_ckpt_destroy (waits for the drain); raises if the writer failed"""
+        if self.h:
+            rc = lib().shud_ckpt_destroy(self.h)
+            self.h = None
+            _check(rc, "shud_ckpt_destroy")
 
     def __del__(self):
         try:

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import abi
-from .runtime import OdeSolver, ShudRhsError
+from .runtime import Checkpoint, OdeSolver, ShudRhsError
 
 ZERO = 1.0e-10                      # Macros.hpp:32
 
@@ -46,12 +46,42 @@ class ShudSolver:
         self.h = handle
         self.ctl = ctl
         self.t = ctl.start
+        self.step = 0                   # solver steps taken since ctl.start (a resumed solver continues the count)
+        self._ckpt = None
+        self._wb = None                 # the WaterBalance a run() was given (a checkpoint is then refused)
         self.ode = OdeSolver(handle, ctl.start, y0, ctl.reltol, ctl.abstol, ctl.init_step, ctl.max_step,
                              ctl.min_step, ctl.max_num_steps)
         self.y = None
         # the handle runs in an internal element order (RhsHandle(order=)): device vectors are carried to the model's
         self._ordered = getattr(handle, "ordered", False)
         self.quad_steps = 0             # monitor steps of run(quad=True)
+
+    @classmethod
+    def resume(cls, handle, ctl: SolverControl, path, output=None, monitors=None):
+        """A solver that continues from the checkpoint at `path` (include/shud_ckpt.h): handle (with its ET prelude
+        attached), output (controls added after Output.resume()) and monitors (after RunMonitors.resume()) are built as
+        for a new run and take the file's state; self.t and self.step are the snapshot's.  The forcing callback of the
+        continued run() must recompute the terrain-radiation samples of its first interval (SHUD_TSR_RECOMPUTE)."""
+        self = cls(handle, np.zeros(handle.num_y), ctl)
+        try:
+            self.t, self.step = Checkpoint.restore(path, self.ode, rhs=handle, output=output, monitors=monitors)
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    def snapshot(self, path, output=None, monitors=None):
+        """checkpoint of the run at the current solver-step boundary, after that step's export and monitors; returns
+        once the device pass is enqueued (flush_snapshot() waits for the file)"""
+        if self._ckpt is None:
+            self._ckpt = Checkpoint(stream=self.h.stream())
+        # a run that used water-balance diagnostics is refused by the library (SHUD_ERR_UNSUPPORTED)
+        self._ckpt.snapshot(path, self.t, self.step, self.ode, rhs=self.h, output=output, monitors=monitors,
+                            wb=self._wb)
+
+    def flush_snapshot(self):
+        if self._ckpt is not None:
+            self._ckpt.flush()
 
     def run(self, num_steps, forcing=None, on_output=None, output=None, wb=None, quad=False):
         """On an ordered handle (RhsHandle(order=)) y0 and the y of on_output are in the model's numbering; `output`
@@ -79,6 +109,8 @@ class ShudSolver:
         ordered = self._ordered
         if ordered and wb is not None:
             raise ValueError("water-balance diagnostics are not available on an ordered handle")
+        if wb is not None:
+            self._wb = wb
         if output is not None:
             d_y = self._out_y = getattr(self, "_out_y", None) or self.h.device_alloc(8 * self.h.num_y)
         d_du = None
@@ -128,6 +160,7 @@ class ShudSolver:
                     wb.sample(self.t, d_du)
                     wb.maybe_write(self.t)
                 output.export(self.t)
+            self.step += 1
             if on_output is not None:
                 if self.y is None:
                     src = d_y
@@ -150,6 +183,9 @@ class ShudSolver:
         return self.ode.stats()
 
     def close(self):
+        if self._ckpt is not None:
+            self._ckpt.close()
+            self._ckpt = None
         self.ode.close()
         for name in ("_out_y", "_wb_du", "_cal_y"):
             if getattr(self, name, None):
