@@ -52,9 +52,6 @@
 // files are reproducible.  With --reorder the slab is built from the control's buffer, which is in the input's column
 // order already.  A project without the key makes exactly the calls it made before.
 // Not restated (out of the device path's scope): the screen print, NetCDF forcing, the uncoupled -g mode.
-#include <strings.h>
-#include <sys/stat.h>
-
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -65,6 +62,7 @@
 #include <vector>
 
 #include "shud_et.h"
+#include "shud_gpu_util.hpp"
 #include "shud_host.h"
 #include "shud_ckpt.h"
 #include "shud_mon.h"
@@ -102,27 +100,6 @@ static void usage() {
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
                            bool quiet);
 
-static int mkdirs(const std::string &d) {
-    std::string cur;
-    for (size_t i = 0; i <= d.size(); i++) {
-        if (i == d.size() || d[i] == '/') {
-            if (!cur.empty()) mkdir(cur.c_str(), 0755);
-        }
-        if (i < d.size()) cur += d[i];
-    }
-    struct stat st;
-    return stat(d.c_str(), &st) == 0 ? 0 : -1;
-}
-
-// env_truthy (WaterBalanceDiag.cpp:21-36): unset, "", "0", "false" and "off" (any case) are false
-static bool env_truthy(const char *s) {
-    if (s == nullptr || s[0] == '\0') return false;
-    if (strcmp(s, "0") == 0) return false;
-    if (strcasecmp(s, "false") == 0) return false;
-    if (strcasecmp(s, "off") == 0) return false;
-    return true;
-}
-
 // the SHUD_ARR_* arrays indexed by element (the others are per reach or per lake)
 static bool arr_is_ele(int a) {
     switch (a) {
@@ -138,15 +115,85 @@ static bool arr_is_ele(int a) {
 
 static const char *lonlat_name(int m) { return m == 1 ? "FORCING_MEAN" : (m == 2 ? "FIXED" : "FORCING_FIRST"); }
 
-int main(int argc, char **argv) {
-    std::string outdir, cwd;
+// One run: what main() held as locals.  The stages below are main()'s blocks, in its order, under the names of their
+// Python counterparts (shud_rhs/driver.py); a stage that fails has printed its message and returns the exit code, and
+// main() returns it as it did before: nothing is torn down on a failure path.
+struct Run {
+    // ---- the command line ----
+    std::string outdir, cwd, reorder, ckpt_path, resume_path;
+    const char *indir = nullptr, *prj = nullptr;
     double end_day = -1.0;
-    long long max_steps = -1;
-    bool quiet = false;
+    long long max_steps = -1, ckpt_every = 0;
+    bool quiet = false, rhs_bench = false, want_flood = false, want_ic = false, want_ckpt = false;
     int rhs_check = 0, evals = 0;
-    bool rhs_bench = false, want_flood = false, want_ic = false;
-    std::string reorder, ckpt_path, resume_path;
-    long long ckpt_every = 0;
+    std::chrono::steady_clock::time_point wall0, loop0;
+    // ---- the project, and with --reorder the planned element order ----
+    shud_project_t p = nullptr;
+    ShudControl c;
+    ShudMeshSoA mesh;
+    ShudParamsSoA par;
+    int64_t ny = 0;
+    const double *y0 = nullptr, *y_is = nullptr, *y_snow = nullptr;              // in the device side's order
+    // the input's own arrays: what .cfg.ic.bak and the first snapshot are written from, in the input's numbering
+    const double *y0_in = nullptr, *y_is_in = nullptr, *y_snow_in = nullptr;
+    std::vector<int32_t> perm, inv;
+    shud_ordered_t ordered = nullptr;
+    std::vector<std::vector<int32_t>> o_int;
+    std::vector<std::vector<double>> o_dbl;
+    // ---- the device side ----
+    shud_rhs_t h = nullptr;
+    ShudEtMeshSoA etm;
+    ShudEtParams etp;
+    shud_ode_t ode = nullptr;
+    double *d_y = nullptr, *d_du = nullptr;
+    shud_out_t out = nullptr;
+    ShudNcOutputCfg ncc;
+    std::vector<ShudOutputDecl> decl;
+    int nprint = 0;
+    shud_wb_t wb = nullptr;
+    bool quad = false;
+    long long quad_steps = 0;
+    shud_mon_t mon = nullptr;
+    std::string ic_update;
+    long long ic_snaps = 0;
+    std::thread ic0;
+    int ic0_rc = 0;
+    shud_ckpt_t ckpt = nullptr;
+    // ---- the loop: the loop index, -n and -e count from the original start ----
+    long long i0 = 0, nsteps = 0;
+    double t = 0.0, tnext = 0.0;
+    int rc = 0;
+    // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
+    // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag, quad monitor (its f(), replay and pass)
+    // run monitors (their enqueue; the writer thread's own time is reported beside it)
+    double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::chrono::steady_clock::time_point tick;
+
+    int parse_args(int argc, char **argv);
+    int load_project();
+    int device_model();
+    int add_outputs();
+    int water_balance();
+    int monitors();
+    int checkpoint_resume();
+    void time_loop();
+    int report();
+
+    void gather_i(const int32_t *&a);
+    void gather_d(const double *&a, int planes, size_t tail);
+    int ic_from_host(const std::string &fn, double th);
+    int ic0_join();
+    int ic_update_at(double tt, bool stepped);
+    int checkpoint(long long step);
+    void lap(int k) {
+        const auto now = std::chrono::steady_clock::now();
+        ph[k] += std::chrono::duration<double>(now - tick).count();
+        tick = now;
+    }
+};
+
+// ---- argument parsing and refusals -> -1 to go on, else the exit code ----
+int Run::parse_args(int argc, char **argv) {
     std::vector<const char *> pos;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -168,7 +215,8 @@ int main(int argc, char **argv) {
         else pos.push_back(argv[i]);
     }
     if (pos.size() != 2) { usage(); return 1; }
-    const char *indir = pos[0], *prj = pos[1];
+    indir = pos[0];
+    prj = pos[1];
     if (outdir.empty()) outdir = std::string("output/") + prj + ".out";
     if (!reorder.empty() && reorder != "bfs" && reorder != "tiles") {
         fprintf(stderr, "--reorder: unknown order '%s' (bfs, tiles)\n", reorder.c_str());
@@ -179,7 +227,7 @@ int main(int argc, char **argv) {
                         "run in another element order\n");
         return 1;
     }
-    const bool want_ckpt = !ckpt_path.empty() || !resume_path.empty();
+    want_ckpt = !ckpt_path.empty() || !resume_path.empty();
     if (ckpt_every < 0 || (ckpt_every > 0 && ckpt_path.empty())) {
         fprintf(stderr, "--checkpoint-every N needs N >= 1 and --checkpoint PATH\n");
         return 1;
@@ -189,51 +237,35 @@ int main(int argc, char **argv) {
                         "accumulators of its own, which a checkpoint does not hold\n");
         return 1;
     }
-    const auto wall0 = std::chrono::steady_clock::now();
+    wall0 = std::chrono::steady_clock::now();
+    return -1;
+}
 
-    // ---- loadinput + initialize + LoadIC (shud.cpp:49-64) ----
-    shud_project_t p = nullptr;
-    if (shud_project_load(indir, prj, cwd.empty() ? nullptr : cwd.c_str(), end_day, &p)) {
-        fprintf(stderr, "%s\n", shud_project_error());
-        return 1;
-    }
-    if (rhs_check > 0 || rhs_bench) {
-        const int rc = shud_gpu_rhs_partition(p, rhs_check, rhs_bench, evals > 0 ? evals : (rhs_bench ? 100 : 6),
-                                              outdir, quiet);
-        shud_project_free(p);
-        return rc;
-    }
-    ShudControl c;
+// a per-element host array (then `tail` more values, copied) carried into the planned order
+void Run::gather_i(const int32_t *&a) {
+    if (!a) return;
+    o_int.emplace_back(perm.size());
+    shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(int32_t), 1, a, o_int.back().data());
+    a = o_int.back().data();
+}
+
+void Run::gather_d(const double *&a, int planes, size_t tail) {
+    if (!a) return;
+    const size_t n = (size_t)planes * perm.size();
+    o_dbl.emplace_back(n + tail);
+    shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(double), planes, a, o_dbl.back().data());
+    std::copy(a + n, a + n + tail, o_dbl.back().begin() + n);
+    a = o_dbl.back().data();
+}
+
+// ---- the loaded project (loadinput + initialize + LoadIC, shud.cpp:49-64) and --reorder ----
+int Run::load_project() {
     shud_project_control(p, &c);
-    ShudMeshSoA mesh;
-    ShudParamsSoA par;
     shud_project_mesh(p, &mesh, &par);
-    int64_t ny = 0;
-    const double *y0 = shud_project_array(p, "y0", &ny);
-    const double *y_is = shud_project_array(p, "y_is", nullptr);
-    const double *y_snow = shud_project_array(p, "y_snow", nullptr);
-    // the input's own arrays: what .cfg.ic.bak and the first snapshot are written from, in the input's numbering
-    const double *const y0_in = y0, *const y_is_in = y_is, *const y_snow_in = y_snow;
+    y0_in = y0 = shud_project_array(p, "y0", &ny);
+    y_is_in = y_is = shud_project_array(p, "y_is", nullptr);
+    y_snow_in = y_snow = shud_project_array(p, "y_snow", nullptr);
     // ---- --reorder: the model, the ET mesh and the initial state in the planned element order ----
-    std::vector<int32_t> perm, inv;
-    shud_ordered_t ordered = nullptr;
-    std::vector<std::vector<int32_t>> o_int;
-    std::vector<std::vector<double>> o_dbl;
-    // a per-element host array (then `tail` more values, copied) carried into the planned order
-    auto gi = [&](const int32_t *&a) {
-        if (!a) return;
-        o_int.emplace_back(perm.size());
-        shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(int32_t), 1, a, o_int.back().data());
-        a = o_int.back().data();
-    };
-    auto gd = [&](const double *&a, int planes, size_t tail) {
-        if (!a) return;
-        const size_t n = (size_t)planes * perm.size();
-        o_dbl.emplace_back(n + tail);
-        shud_order_gather_host(perm.data(), (int32_t)perm.size(), sizeof(double), planes, a, o_dbl.back().data());
-        std::copy(a + n, a + n + tail, o_dbl.back().begin() + n);
-        a = o_dbl.back().data();
-    };
     if (!reorder.empty()) {
         const int ne = mesh.num_ele;
         perm.resize((size_t)ne);
@@ -241,75 +273,59 @@ int main(int argc, char **argv) {
         ShudMeshSoA pm;
         ShudParamsSoA pp;
         if (shud_order_plan(&mesh, reorder == "tiles" ? SHUD_ORDER_TILES : SHUD_ORDER_BFS, nullptr, perm.data()) ||
-            shud_order_apply(&mesh, &par, perm.data(), &ordered, &pm, &pp)) {
-            fprintf(stderr, "--reorder: %s\n", shud_rhs_last_error_string());
-            return 1;
-        }
+            shud_order_apply(&mesh, &par, perm.data(), &ordered, &pm, &pp))
+            return fail("--reorder");
         mesh = pm;
         par = pp;
         for (int k = 0; k < ne; k++) inv[perm[k]] = k;
-        gd(y0, 3, (size_t)(ny - 3 * (int64_t)ne));
-        gd(y_is, 1, 0);
-        gd(y_snow, 1, 0);
+        gather_d(y0, 3, (size_t)(ny - 3 * (int64_t)ne));
+        gather_d(y_is, 1, 0);
+        gather_d(y_snow, 1, 0);
     }
     if (!quiet)
         printf("* \t Project: %s  NumEle %d  NumRiv %d  NumSeg %d  NumLake %d  NY %lld\n"
                "* \t StartTime %.1f  EndTime %.1f [min]  SolverStep %.1f  ETStep %.1f  NumSteps %lld\n",
                prj, mesh.num_ele, mesh.num_riv, mesh.num_seg, mesh.num_lake, (long long)ny, c.start_time,
                c.end_time, c.solver_step, c.et_step, (long long)c.num_steps);
+    return 0;
+}
 
-    // ---- the device side: RHS handle, ET prelude, integrator (SetCVODE, cvode_config.cpp:149-197) ----
+// ---- the device side: RHS handle, ET prelude, integrator (SetCVODE, cvode_config.cpp:149-197) ----
+int Run::device_model() {
     ShudRhsOptions ro = {SHUD_MODE_SERIAL, 0, nullptr, 1};
-    shud_rhs_t h = nullptr;
-    if (shud_rhs_create(&mesh, &par, &ro, &h)) {
-        fprintf(stderr, "shud_rhs_create: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
-    ShudEtMeshSoA etm;
-    ShudEtParams etp;
+    if (shud_rhs_create(&mesh, &par, &ro, &h)) return fail("shud_rhs_create");
     shud_project_et(p, &etm, &etp);
     if (!perm.empty()) {
-        gi(etm.iforc); gi(etm.ilc); gi(etm.imf); gi(etm.ilake);
-        gd(etm.z_surf, 1, 0); gd(etm.albedo, 1, 0); gd(etm.fix_pressure, 1, 0); gd(etm.wind_h, 1, 0);
-        gd(etm.veg_frac, 1, 0); gd(etm.nx, 1, 0); gd(etm.ny, 1, 0); gd(etm.nz, 1, 0);
+        gather_i(etm.iforc); gather_i(etm.ilc); gather_i(etm.imf); gather_i(etm.ilake);
+        gather_d(etm.z_surf, 1, 0); gather_d(etm.albedo, 1, 0); gather_d(etm.fix_pressure, 1, 0);
+        gather_d(etm.wind_h, 1, 0); gather_d(etm.veg_frac, 1, 0); gather_d(etm.nx, 1, 0); gather_d(etm.ny, 1, 0);
+        gather_d(etm.nz, 1, 0);
     }
-    if (shud_et_attach(h, &etm, &etp) || shud_et_set_state(h, y_is, y_snow)) {
-        fprintf(stderr, "shud_et_attach: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
+    if (shud_et_attach(h, &etm, &etp) || shud_et_set_state(h, y_is, y_snow)) return fail("shud_et_attach");
     // carried u_satn before the first RHS: updateforcing's updateElement on f_update's globals, which are
     // freshly allocated (zero) before the first f() call -> u_satn = 0 (satn of an empty column)
     std::vector<double> zeros(mesh.num_ele, 0.0);
     ShudStepInputs si = {};
     si.u_satn = zeros.data();
-    if (shud_rhs_set_step_inputs(h, &si)) {
-        fprintf(stderr, "shud_rhs_set_step_inputs: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
+    if (shud_rhs_set_step_inputs(h, &si)) return fail("shud_rhs_set_step_inputs");
     ShudOdeOptions oo = {c.reltol, c.abstol, c.init_step, c.max_step, 1e-6, 1000000, 0, 0};
-    shud_ode_t ode = nullptr;
-    if (shud_ode_create(h, c.start_time, y0, SHUD_WHERE_HOST, &oo, &ode)) {
-        fprintf(stderr, "shud_ode_create: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
-    double *d_y = nullptr;
+    if (shud_ode_create(h, c.start_time, y0, SHUD_WHERE_HOST, &oo, &ode)) return fail("shud_ode_create");
     if (shud_rhs_device_alloc(h, (size_t)ny * sizeof(double), (void **)&d_y) ||
-        shud_rhs_memcpy(h, d_y, y0, (size_t)ny * sizeof(double), 1)) {
-        fprintf(stderr, "device alloc: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
+        shud_rhs_memcpy(h, d_y, y0, (size_t)ny * sizeof(double), 1))
+        return fail("device alloc");
+    return 0;
+}
 
-    // ---- initialize_output (MD_initialize.cpp:246-345) with device sources ----
+// ---- initialize_output (MD_initialize.cpp:246-345) with device sources ----
+int Run::add_outputs() {
     if (mkdirs(outdir)) {
         fprintf(stderr, "cannot create output directory %s\n", outdir.c_str());
         return 1;
     }
     shud_rhs_prepare_outputs(h);
     shud_rhs_summary(h, d_y);
-    shud_out_t out = nullptr;
     shud_out_create(0, shud_rhs_stream(h), &out);
     // ---- NetcdfOutputContext (MD_initialize.cpp:346-347): the three files, attached when the mode asks for them ----
-    ShudNcOutputCfg ncc;
     shud_project_ncoutput(p, &ncc);
     static const char *mode_name[3] = {"LEGACY", "NETCDF", "BOTH"};
     if (!quiet) printf("* \t OUTPUT_MODE: %s\n", mode_name[ncc.output_mode]);      // Model_Control.cpp:641-643
@@ -330,16 +346,12 @@ int main(int argc, char **argv) {
             ShudNcSpec ns = {k, n_of[k], ncc.out_dir, (int64_t)c.forc_start_time, hist && hist[0] ? hist : nullptr,
                              ncc.crs_wkt, (int32_t)nnode, node_x, node_y, shud_project_ele_nodes(p, nullptr),
                              shud_project_array(p, "x", nullptr), shud_project_array(p, "y", nullptr)};
-            if (shud_out_attach_nc(out, &ns)) {
-                fprintf(stderr, "shud_out_attach_nc: %s\n", shud_rhs_last_error_string());
-                return 1;
-            }
+            if (shud_out_attach_nc(out, &ns)) return fail("shud_out_attach_nc");
         }
     }
     const int nd = shud_project_outputs(p, outdir.c_str(), nullptr, 0);
-    std::vector<ShudOutputDecl> decl(nd);
+    decl.resize(nd);
     shud_project_outputs(p, outdir.c_str(), decl.data(), nd);
-    int nprint = 0;
     for (const auto &d : decl) {
         int64_t n = 0;
         const double *src = shud_rhs_device_array(h, d.array, &n);
@@ -374,16 +386,12 @@ int main(int argc, char **argv) {
         nprint++;
     }
     // the NetCDF headers and fixed variables (the mesh): before the time loop, not inside its first export
-    if (ncc.output_mode != 0 && shud_out_nc_begin(out)) {
-        fprintf(stderr, "shud_out_nc_begin: %s\n", shud_rhs_last_error_string());
-        return 1;
-    }
+    if (ncc.output_mode != 0 && shud_out_nc_begin(out)) return fail("shud_out_nc_begin");
+    return 0;
+}
 
-    // ---- WaterBalanceDiag::enable (shud.cpp:70-75): shud.cpp:72's test, then openFiles' env_truthy ----
-    shud_wb_t wb = nullptr;
-    double *d_du = nullptr;
-    bool quad = false;
-    long long quad_steps = 0;
+// ---- WaterBalanceDiag::enable (shud.cpp:70-75): shud.cpp:72's test, then openFiles' env_truthy ----
+int Run::water_balance() {
     const char *wb_env = getenv("SHUD_WB_DIAG");
     if (wb_env != nullptr && wb_env[0] != '\0' && strcmp(wb_env, "0") != 0 && env_truthy(wb_env)) {
         quad = env_truthy(getenv("SHUD_WB_DIAG_QUAD"));       // read only when the diagnostic is on (:271)
@@ -392,32 +400,27 @@ int main(int argc, char **argv) {
                             (int64_t)c.forc_start_time, c.radiation_input_mode, c.terrain_radiation,
                             lonlat_name(c.solar_lonlat_mode), c.solar_lon_deg, c.solar_lat_deg, prefix.c_str()};
         if (shud_wb_create(h, &mesh, &par, &wo, &wb) ||
-            shud_rhs_device_alloc(h, (size_t)ny * sizeof(double), (void **)&d_du)) {
-            fprintf(stderr, "shud_wb_create: %s\n", shud_rhs_last_error_string());
-            return 1;
-        }
-        if (quad && shud_wb_quad_enable(wb)) {
-            fprintf(stderr, "shud_wb_quad_enable: %s\n", shud_rhs_last_error_string());
-            return 1;
-        }
+            shud_rhs_device_alloc(h, (size_t)ny * sizeof(double), (void **)&d_du))
+            return fail("shud_wb_create");
+        if (quad && shud_wb_quad_enable(wb)) return fail("shud_wb_quad_enable");
     }
+    return 0;
+}
 
-    // ---- PrintInit(Init_bak, 0) and InitFloodAlert (shud.cpp:76-77), only with --ic-snapshots / --flood ----
-    shud_mon_t mon = nullptr;
-    const std::string ic_update = outdir + "/" + prj + ".cfg.ic.update";
+// LoadIC's values through the device-free formatter (what the reference's arrays hold before the first step)
+int Run::ic_from_host(const std::string &fn, double th) {
     const int NE = mesh.num_ele, NR = mesh.num_riv, NL = mesh.num_lake;
-    // LoadIC's values through the device-free formatter (what the reference's arrays hold before the first step)
-    auto ic_from_host = [&](const std::string &fn, double th) {
-        return shud_mon_write_ic_host(fn.c_str(), th, NE, NR, NL, y_is_in, y_snow_in, y0_in, y0_in + NE,
-                                      y0_in + 2 * (size_t)NE, y0_in + 3 * (size_t)NE,
-                                      NL ? y0_in + 3 * (size_t)NE + NR : nullptr);
-    };
-    long long ic_snaps = 0;
+    return shud_mon_write_ic_host(fn.c_str(), th, NE, NR, NL, y_is_in, y_snow_in, y0_in, y0_in + NE,
+                                  y0_in + 2 * (size_t)NE, y0_in + 3 * (size_t)NE,
+                                  NL ? y0_in + 3 * (size_t)NE + NR : nullptr);
+}
+
+// ---- PrintInit(Init_bak, 0) and InitFloodAlert (shud.cpp:76-77), only with --ic-snapshots / --flood ----
+int Run::monitors() {
+    ic_update = outdir + "/" + prj + ".cfg.ic.update";
+    const int NE = mesh.num_ele, NR = mesh.num_riv, NL = mesh.num_lake;
     if (want_flood || want_ic) {
-        if (shud_mon_create(0, shud_rhs_stream(h), &mon)) {
-            fprintf(stderr, "shud_mon_create: %s\n", shud_rhs_last_error_string());
-            return 1;
-        }
+        if (shud_mon_create(0, shud_rhs_stream(h), &mon)) return fail("shud_mon_create");
         if (!resume_path.empty()) shud_mon_resume(mon, 1);
         if (want_ic) {
             const std::string bak = outdir + "/" + prj + ".cfg.ic.bak";
@@ -433,59 +436,50 @@ int main(int argc, char **argv) {
                              shud_rhs_device_array(h, SHUD_ARR_Y_ELE_GW, nullptr),
                              shud_rhs_device_array(h, SHUD_ARR_Y_RIV_STG, nullptr),
                              NL ? shud_rhs_device_array(h, SHUD_ARR_Y_LAKE_STG, nullptr) : nullptr};
-            if (shud_mon_add_ic(mon, &is) || (!perm.empty() && shud_mon_set_ic_order(mon, perm.data()))) {
-                fprintf(stderr, "shud_mon_add_ic: %s\n", shud_rhs_last_error_string());
-                return 1;
-            }
+            if (shud_mon_add_ic(mon, &is) || (!perm.empty() && shud_mon_set_ic_order(mon, perm.data())))
+                return fail("shud_mon_add_ic");
         }
         if (want_flood) {
             const std::string fcsv = outdir + "/" + prj + ".flood.csv";
             ShudFloodSpec fs = {fcsv.c_str(), shud_rhs_device_array(h, SHUD_ARR_Y_RIV_STG, nullptr),
                                 shud_rhs_device_array(h, SHUD_ARR_QRIV_DOWN, nullptr), NR, mesh.riv_depth,
                                 shud_project_riv_type(p, nullptr)};
-            if (shud_mon_add_flood(mon, &fs)) {
-                fprintf(stderr, "shud_mon_add_flood: %s\n", shud_rhs_last_error_string());
-                return 1;
-            }
+            if (shud_mon_add_flood(mon, &fs)) return fail("shud_mon_add_flood");
         }
     }
-    // PrintInit(Init_update, t): LoadIC's values until the first step has run (formatted on a thread of its own,
-    // joined before anything else may write the file), the device arrays afterwards
-    std::thread ic0;
-    int ic0_rc = 0;
-    auto ic0_join = [&]() {
-        if (ic0.joinable()) ic0.join();
-        return ic0_rc;
-    };
-    auto ic_update_at = [&](double tt, bool stepped) {
-        int due = ic0_join() ? -1 : 0;
-        if (due == 0 && stepped) {
-            due = shud_mon_ic_update(mon, tt);
-        } else if (due == 0) {
-            const int ustep = shud_project_update_ic_step(p);
-            due = ((unsigned long)(long)tt) % (unsigned long)ustep == 0;
-            if (due) ic0 = std::thread([&ic0_rc, &ic_from_host, &ic_update, tt] { ic0_rc = ic_from_host(ic_update, tt); });
-        }
-        if (due < 0) {
-            fprintf(stderr, "restart snapshot at t = %f: %s\n", tt, shud_rhs_last_error_string());
-            return 1;
-        }
-        ic_snaps += due;
-        return 0;
-    };
+    return 0;
+}
 
-    // ---- the time loop (shud.cpp:86-140) ----
-    shud_rhs_synchronize(h);
-    const auto loop0 = std::chrono::steady_clock::now();
-    const bool et_sub = c.et_step > kZero && c.et_step + kZero < c.solver_step;
-    double t = c.start_time, tnext = t;
-    const long long nsteps = max_steps >= 0 && max_steps < c.num_steps ? max_steps : c.num_steps;
-    int rc = 0;
-    // ---- --checkpoint / --resume (include/shud_ckpt.h): the loop index, -n and -e count from the original start ----
-    shud_ckpt_t ckpt = nullptr;
-    const ShudCkptParts parts = {h, ode, out, mon, wb};
-    long long i0 = 0;
+// PrintInit(Init_update, t): LoadIC's values until the first step has run (formatted on a thread of its own,
+// joined before anything else may write the file), the device arrays afterwards
+int Run::ic0_join() {
+    if (ic0.joinable()) ic0.join();
+    return ic0_rc;
+}
+
+int Run::ic_update_at(double tt, bool stepped) {
+    int due = ic0_join() ? -1 : 0;
+    if (due == 0 && stepped) {
+        due = shud_mon_ic_update(mon, tt);
+    } else if (due == 0) {
+        const int ustep = shud_project_update_ic_step(p);
+        due = ((unsigned long)(long)tt) % (unsigned long)ustep == 0;
+        if (due) ic0 = std::thread([this, tt] { ic0_rc = ic_from_host(ic_update, tt); });
+    }
+    if (due < 0) {
+        fprintf(stderr, "restart snapshot at t = %f: %s\n", tt, shud_rhs_last_error_string());
+        return 1;
+    }
+    ic_snaps += due;
+    return 0;
+}
+
+// ---- --checkpoint / --resume (include/shud_ckpt.h), inside the timed part of the run ----
+int Run::checkpoint_resume() {
+    t = c.start_time, tnext = t;
+    nsteps = max_steps >= 0 && max_steps < c.num_steps ? max_steps : c.num_steps;
     if (!resume_path.empty()) {
+        const ShudCkptParts parts = {h, ode, out, mon, wb};
         int64_t step = 0;
         if (shud_ckpt_restore(resume_path.c_str(), &parts, &t, &step)) {
             fprintf(stderr, "--resume %s: %s\n", resume_path.c_str(), shud_rhs_last_error_string());
@@ -495,27 +489,23 @@ int main(int argc, char **argv) {
         tnext = t;
         if (!quiet) printf("* \t resumed from %s: solver step %lld, t = %.3f min\n", resume_path.c_str(), i0, t);
     }
-    if (!ckpt_path.empty() && shud_ckpt_create(0, shud_rhs_stream(h), &ckpt)) {
-        fprintf(stderr, "shud_ckpt_create: %s\n", shud_rhs_last_error_string());
+    if (!ckpt_path.empty() && shud_ckpt_create(0, shud_rhs_stream(h), &ckpt)) return fail("shud_ckpt_create");
+    return 0;
+}
+
+int Run::checkpoint(long long step) {
+    const ShudCkptParts parts = {h, ode, out, mon, wb};
+    if (shud_ckpt_snapshot(ckpt, &parts, t, step, ckpt_path.c_str())) {
+        fprintf(stderr, "--checkpoint %s: %s\n", ckpt_path.c_str(), shud_rhs_last_error_string());
         return 1;
     }
-    auto checkpoint = [&](long long step) {
-        if (shud_ckpt_snapshot(ckpt, &parts, t, step, ckpt_path.c_str())) {
-            fprintf(stderr, "--checkpoint %s: %s\n", ckpt_path.c_str(), shud_rhs_last_error_string());
-            return 1;
-        }
-        return 0;
-    };
-    // wall time per phase of the loop (host view: includes waiting on the device where a phase synchronizes)
-    // forcing+BC rows, ET step, CVode, summary+diagnostics, export, wb diag, quad monitor (its f(), replay and pass)
-    // run monitors (their enqueue; the writer thread's own time is reported beside it)
-    double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto tick = std::chrono::steady_clock::now();
-    auto lap = [&](int k) {
-        const auto now = std::chrono::steady_clock::now();
-        ph[k] += std::chrono::duration<double>(now - tick).count();
-        tick = now;
-    };
+    return 0;
+}
+
+// ---- the time loop (shud.cpp:86-140), the final checkpoint and the restart snapshot after it (shud.cpp:157) ----
+void Run::time_loop() {
+    const bool et_sub = c.et_step > kZero && c.et_step + kZero < c.solver_step;
+    tick = std::chrono::steady_clock::now();
     for (long long i = i0; i < nsteps && !rc; i++) {
         if (want_ic) {                            // MD->PrintInit(fout->Init_update, t)
             if (ic_update_at(t, i > 0)) {
@@ -642,6 +632,10 @@ int main(int argc, char **argv) {
         if (ic_update_at(t, nsteps > 0 || i0 > 0)) rc = 1;
         lap(7);
     }
+}
+
+// ---- the final report and the JSON line; everything is flushed and torn down -> the exit code ----
+int Run::report() {
     shud_rhs_synchronize(h);
     const double loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop0).count();
     shud_out_destroy(out);
@@ -703,4 +697,27 @@ int main(int argc, char **argv) {
     if (ordered) shud_order_free(ordered);
     shud_project_free(p);
     return rc;
+}
+
+int main(int argc, char **argv) {
+    Run r;
+    const int arc = r.parse_args(argc, argv);
+    if (arc >= 0) return arc;
+    // ---- loadinput + initialize + LoadIC (shud.cpp:49-64) ----
+    if (shud_project_load(r.indir, r.prj, r.cwd.empty() ? nullptr : r.cwd.c_str(), r.end_day, &r.p)) {
+        fprintf(stderr, "%s\n", shud_project_error());
+        return 1;
+    }
+    if (r.rhs_check > 0 || r.rhs_bench) {
+        const int rc = shud_gpu_rhs_partition(r.p, r.rhs_check, r.rhs_bench,
+                                              r.evals > 0 ? r.evals : (r.rhs_bench ? 100 : 6), r.outdir, r.quiet);
+        shud_project_free(r.p);
+        return rc;
+    }
+    if (r.load_project() || r.device_model() || r.add_outputs() || r.water_balance() || r.monitors()) return 1;
+    shud_rhs_synchronize(r.h);
+    r.loop0 = std::chrono::steady_clock::now();
+    if (r.checkpoint_resume()) return 1;
+    r.time_loop();
+    return r.report();
 }

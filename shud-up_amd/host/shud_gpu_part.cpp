@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "shud_et.h"
+#include "shud_gpu_util.hpp"
 #include "shud_host.h"
 #include "shud_partition.h"
 #include "shud_rhs.h"
@@ -47,10 +48,8 @@ struct Rank {
     std::vector<double> z_surf, albedo, fix_p, wind_h, veg, nx, ny, nz, y_is, y_snow;
 };
 
-int fail(const char *what) {
-    fprintf(stderr, "%s: %s %s\n", what, shud_rhs_last_error_string(), shud_partition_error());
-    return 1;
-}
+// a failed call of either library: both last errors
+int part_fail(const char *what) { return fail(what, shud_partition_error()); }
 
 // the project's ET statics gathered to a rank's local elements
 ShudEtMeshSoA local_et(Rank &r, const ShudEtMeshSoA &g) {
@@ -87,12 +86,12 @@ ShudEtMeshSoA local_et(Rank &r, const ShudEtMeshSoA &g) {
 // attach the ET prelude, IC storages and u_satn = 0 (as the driver does before the first RHS), run one ET step
 int prepare_handle(shud_rhs_t h, const ShudEtMeshSoA &etm, const ShudEtParams &etp, const double *y_is,
                    const double *y_snow, int ne, ShudEtForcing *f) {
-    if (shud_et_attach(h, &etm, &etp) || shud_et_set_state(h, y_is, y_snow)) return fail("shud_et_attach");
+    if (shud_et_attach(h, &etm, &etp) || shud_et_set_state(h, y_is, y_snow)) return part_fail("shud_et_attach");
     std::vector<double> zeros(ne, 0.0);
     ShudStepInputs si = {};
     si.u_satn = zeros.data();
-    if (shud_rhs_set_step_inputs(h, &si)) return fail("shud_rhs_set_step_inputs");
-    if (shud_et_step(h, f)) return fail("shud_et_step");
+    if (shud_rhs_set_step_inputs(h, &si)) return part_fail("shud_rhs_set_step_inputs");
+    if (shud_et_step(h, f)) return part_fail("shud_et_step");
     return 0;
 }
 
@@ -150,16 +149,6 @@ std::string read_id_file(const std::string &f, const std::string &token, time_t 
     return s.substr(token.size() + 1);
 }
 
-int mkdirs(const std::string &d) {
-    std::string cur;
-    for (size_t i = 0; i <= d.size(); i++) {
-        if ((i == d.size() || d[i] == '/') && !cur.empty()) mkdir(cur.c_str(), 0755);
-        if (i < d.size()) cur += d[i];
-    }
-    struct stat st;
-    return stat(d.c_str(), &st) == 0 ? 0 : -1;
-}
-
 }  // namespace
 
 int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int nevals, const std::string &outdir,
@@ -195,25 +184,25 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
     ShudPartStats st{};
     const auto tp = std::chrono::steady_clock::now();
     if (K > 1 && shud_partition_mesh(&mesh, cx, cy, K, SHUD_PART_AUTO, 12345, ele_part.data(), &st))
-        return fail("shud_partition_mesh");
+        return part_fail("shud_partition_mesh");
     const double part_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tp).count();
 
     if (!bench) {
         // ======== --rhs-check K: all parts in this process on one GPU, D2D halo ========
         ShudRhsOptions ro = {SHUD_MODE_SERIAL, 0, nullptr, 1};
         shud_rhs_t g = nullptr;
-        if (shud_rhs_create(&mesh, &par, &ro, &g)) return fail("shud_rhs_create");
+        if (shud_rhs_create(&mesh, &par, &ro, &g)) return part_fail("shud_rhs_create");
         if (prepare_handle(g, etm, etp, y_is, y_snow, NE, &f)) return 1;
         std::vector<Rank> R(K);
         for (int r = 0; r < K; r++) {
             Rank &q = R[r];
             if (shud_plan_build(&mesh, ele_part.data(), K, r, &q.plan) || shud_plan_partition(q.plan, &q.part) ||
                 shud_plan_local_mesh(q.plan, &mesh, &par, &q.lmesh, &q.lpar))
-                return fail("shud_plan");
+                return part_fail("shud_plan");
             q.ne = q.lmesh.num_ele;
             q.n_own = q.part.n_own_ele;
             q.n_own_riv = q.part.n_own_riv;
-            if (shud_rhs_create_partitioned(&q.lmesh, &q.lpar, &ro, &q.part, &q.h)) return fail("create_partitioned");
+            if (shud_rhs_create_partitioned(&q.lmesh, &q.lpar, &ro, &q.part, &q.h)) return part_fail("create_partitioned");
             std::vector<double> lis(q.ne), lsn(q.ne);
             shud_plan_gather_ele(q.plan, y_is, lis.data());
             shud_plan_gather_ele(q.plan, y_snow, lsn.data());
@@ -227,7 +216,7 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
             q.ref_own.resize(no);
             if (shud_rhs_device_alloc(q.h, no * 8, (void **)&q.d_y) || shud_rhs_device_alloc(q.h, no * 8, (void **)&q.d_dy) ||
                 shud_rhs_halo_buffers(q.h, &q.esend, &q.rsend, &q.gele, &q.griv))
-                return fail("device buffers");
+                return part_fail("device buffers");
         }
         std::vector<double> dy(ny);
         long long mismatched = 0;
@@ -235,13 +224,13 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
         for (int e = 0; e < nevals; e++) {
             const std::vector<double> y = test_state(y0, ny, NE, e / 3);   // 3 successive calls per state
             auto t0 = std::chrono::steady_clock::now();
-            if (shud_rhs_eval(g, 0.0, y.data(), dy.data(), SHUD_WHERE_HOST)) return fail("shud_rhs_eval");
+            if (shud_rhs_eval(g, 0.0, y.data(), dy.data(), SHUD_WHERE_HOST)) return part_fail("shud_rhs_eval");
             t_one += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             t0 = std::chrono::steady_clock::now();
             for (auto &q : R) {
                 shud_plan_owned_state(q.plan, y.data(), NE, q.y_own.data());
                 shud_rhs_memcpy(q.h, q.d_y, q.y_own.data(), q.y_own.size() * 8, 1);
-                if (shud_rhs_eval_pack(q.h, q.d_y)) return fail("eval_pack");
+                if (shud_rhs_eval_pack(q.h, q.d_y)) return part_fail("eval_pack");
                 shud_rhs_synchronize(q.h);
             }
             for (int r = 0; r < K; r++) {                     // the all-to-all-v as D2D copies
@@ -252,15 +241,15 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
                     const int e0 = src.part.ele_send_off[r], e1 = src.part.ele_send_off[r + 1];
                     const int d0 = q.part.ele_recv_off[s];
                     if (e1 > e0 && shud_rhs_memcpy(q.h, q.gele + 3 * (size_t)d0, src.esend + 3 * (size_t)e0,
-                                                   24 * (size_t)(e1 - e0), 3)) return fail("halo copy");
+                                                   24 * (size_t)(e1 - e0), 3)) return part_fail("halo copy");
                     const int r0 = src.part.riv_send_off[r], r1 = src.part.riv_send_off[r + 1];
                     const int q0 = q.part.riv_recv_off[s];
                     if (r1 > r0 && shud_rhs_memcpy(q.h, q.griv + q0, src.rsend + r0, 8 * (size_t)(r1 - r0), 3))
-                        return fail("halo copy");
+                        return part_fail("halo copy");
                 }
             }
             for (auto &q : R) {
-                if (shud_rhs_eval_compute(q.h, 0.0, q.d_y, q.d_dy)) return fail("eval_compute");
+                if (shud_rhs_eval_compute(q.h, 0.0, q.d_y, q.d_dy)) return part_fail("eval_compute");
                 shud_rhs_memcpy(q.h, q.dy_own.data(), q.d_dy, q.dy_own.size() * 8, 2);
                 shud_rhs_synchronize(q.h);
             }
@@ -301,7 +290,7 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
     std::string nccl_id;
     shud_rhs_t h = nullptr;
     if (K == 1) {
-        if (shud_rhs_create(&mesh, &par, &ro, &h)) return fail("shud_rhs_create");
+        if (shud_rhs_create(&mesh, &par, &ro, &h)) return part_fail("shud_rhs_create");
         if (prepare_handle(h, etm, etp, y_is, y_snow, NE, &f)) return 1;
         q.n_own = NE;
         q.n_own_riv = mesh.num_riv;
@@ -312,7 +301,7 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
         if (rank == 0) {
             unlink(idf.c_str());                              // never leave an earlier job's id in place
             char id[128];
-            if (shud_rhs_nccl_unique_id(id)) return fail("nccl id");
+            if (shud_rhs_nccl_unique_id(id)) return part_fail("nccl id");
             const std::string tmp = idf + ".tmp";
             FILE *fp = fopen(tmp.c_str(), "wb");
             if (!fp || fwrite(token.data(), 1, token.size(), fp) != token.size() || fputc('\n', fp) == EOF ||
@@ -342,12 +331,12 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
         }
         if (shud_plan_build(&mesh, ele_part.data(), K, rank, &q.plan) || shud_plan_partition(q.plan, &q.part) ||
             shud_plan_local_mesh(q.plan, &mesh, &par, &q.lmesh, &q.lpar))
-            return fail("shud_plan");
+            return part_fail("shud_plan");
         q.part.nccl_unique_id = nccl_id.data();
         q.ne = q.lmesh.num_ele;
         q.n_own = q.part.n_own_ele;
         q.n_own_riv = q.part.n_own_riv;
-        if (shud_rhs_create_partitioned(&q.lmesh, &q.lpar, &ro, &q.part, &h)) return fail("create_partitioned");
+        if (shud_rhs_create_partitioned(&q.lmesh, &q.lpar, &ro, &q.part, &h)) return part_fail("create_partitioned");
         std::vector<double> lis(q.ne), lsn(q.ne);
         shud_plan_gather_ele(q.plan, y_is, lis.data());
         shud_plan_gather_ele(q.plan, y_snow, lsn.data());
@@ -367,14 +356,14 @@ int shud_gpu_rhs_partition(shud_project_t p, int nparts_check, bool bench, int n
     double *d_y = nullptr, *d_dy = nullptr;
     if (shud_rhs_device_alloc(h, no * 8, (void **)&d_y) || shud_rhs_device_alloc(h, no * 8, (void **)&d_dy) ||
         shud_rhs_memcpy(h, d_y, yo.data(), no * 8, 1))
-        return fail("device buffers");
+        return part_fail("device buffers");
     for (int w = 0; w < 5; w++)
-        if (shud_rhs_eval(h, 0.0, d_y, d_dy, SHUD_WHERE_DEVICE)) return fail("eval");
+        if (shud_rhs_eval(h, 0.0, d_y, d_dy, SHUD_WHERE_DEVICE)) return part_fail("eval");
     shud_rhs_synchronize(h);
     shud_rhs_timing(h, nevals, nevals >= 20 ? 5 : 1);
     const auto t0 = std::chrono::steady_clock::now();
     for (int e = 0; e < nevals; e++)
-        if (shud_rhs_eval(h, 0.0, d_y, d_dy, SHUD_WHERE_DEVICE)) return fail("eval");
+        if (shud_rhs_eval(h, 0.0, d_y, d_dy, SHUD_WHERE_DEVICE)) return part_fail("eval");
     shud_rhs_synchronize(h);
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     double me = 0, mr = 0, mv = 0;

@@ -13,11 +13,11 @@ import wb_quad_py
 from conftest import ORACLE_DIR
 from print_ctrl_py import PrintCtrlPy
 from shud_rhs import abi, host
+from shud_rhs.driver import header_kw
 
 sys.path.insert(0, os.path.join(ORACLE_DIR, "ref"))
 import refio  # noqa: E402
 
-LONLAT = {0: "FORCING_FIRST", 1: "FORCING_MEAN", 2: "FIXED"}
 CASES = list(refio.WRITER_CASES)
 # SHUD_ARR_* -> the oracle diagnostic of the same array (RhsHandle.diagnostics() has the same names)
 ARR_DIAG = {abi.SHUD_ARR_QELE_SURF_TOT: "qele_surf_tot", abi.SHUD_ARR_QELE_SUB_TOT: "qele_sub_tot",
@@ -61,11 +61,6 @@ def load(case, tmp_factory):
 
 def project(L):
     return host.Project(L["dir"], L["prj"], cwd=L["work"])
-
-
-def header_kw(c):
-    return dict(radiation_input_mode=c["radiation_input_mode"], terrain_radiation=c["terrain_radiation"],
-                solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"], lat=c["solar_lat_deg"])
 
 
 def same_bits(a, b):

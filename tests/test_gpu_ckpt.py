@@ -10,23 +10,20 @@ import glob
 import os
 import re
 import shutil
-import subprocess
 import zipfile
 
 import numpy as np
 import pytest
 
 import oracle
-from conftest import GOLDEN, PKG_DIR
+import shud_gpu_run
+from conftest import GOLDEN
 import cases
-from shud_rhs import abi, host, partition, synth
+from shud_rhs import abi, driver, partition, synth
 from shud_rhs import runtime as rt
-from shud_rhs.solver import ShudSolver, SolverControl
 from test_gpu_ode import COUNTERS, _dev, device_order, kat  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
-LONLAT = {0: "FORCING_FIRST", 1: "FORCING_MEAN", 2: "FIXED"}
 INTERVALS = (20, 30)                 # output intervals [min]: with 10-minute solver steps 30 does not divide 40 or 10
 
 
@@ -95,53 +92,20 @@ def _project(kind, root):
     return _unzip(prj, root, cryo=kind == "cryo"), prj, root
 
 
-class Run:
+class Run(driver.ProjectRun):
     """one process's worth of objects over a project: handle + ET prelude, output set (.dat and .csv controls at two
     intervals), optionally the monitors; resume=True opens the files of an earlier run"""
 
     def __init__(self, proj, outdir, mode=abi.SHUD_MODE_SERIAL, order=None, resume=False, monitors=False,
                  tweak=None):
         src, prj, cwd = proj
-        self.prj = prj
-        self.P = P = host.Project(src, prj, cwd=cwd)
-        self.c = c = P.control()
         # the projects' own tolerances (1e-4) let ccw and qhh take one internal step per solver step at order 1 for
         # hours; tighter ones make the integrator work inside every solver step, so the order rises within a few
-        self.ctl = SolverControl(reltol=1e-6, abstol=1e-6, init_step=1e-3, max_step=c["max_step"],
-                                 et_step=c["et_step"], start=c["start_time"])
-        self.m = m = P.model()
-        if tweak:
-            tweak(m)
-        self.h = h = rt.RhsHandle(m, mode=mode, order=order)
-        h.et_attach(P.et_model())
-        h.et_set_state(P.array("y_is"), P.array("y_snow"))
-        h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
-        h.prepare_outputs()
-        self.out = self.mon = None
-        self.outdir = str(outdir)
-        os.makedirs(outdir, exist_ok=True)
-        self.out = out = rt.Output(stream=h.stream())
-        # an ordered handle's element arrays are in the internal numbering: column c reads element inv[c]
-        inv = h.order()[2] if h.ordered else None
-        if resume:
-            out.resume()
-        kw = dict(radiation_input_mode=c["radiation_input_mode"], terrain_radiation=c["terrain_radiation"],
-                  solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"], lat=c["solar_lat_deg"])
-        for k, d in enumerate(P.outputs(self.outdir)):
-            p, _ = h.device_array(d["array"])
-            if d["column"] >= 0:
-                p += 8 * d["column"] * m.num_ele
-            out.add(d["basename"], p, d["n_all"], INTERVALS[k % 2], d["iflux"], start_time=c["forc_start_time"],
-                    flag_io=d["flag_io"], binary=True, ascii=k % 3 == 0,
-                    col_src=inv if inv is not None and d["n_all"] == m.num_ele else None, **kw)
-        if monitors:
-            self.mon = mon = rt.RunMonitors(stream=h.stream())
-            if resume:
-                mon.resume()
-            nr = m.num_riv
-            mon.add_flood(os.path.join(self.outdir, "run.flood.csv"), h.device_array(abi.SHUD_ARR_Y_RIV_STG)[0],
-                          h.device_array(abi.SHUD_ARR_QRIV_DOWN)[0], nr, np.zeros(nr), np.ones(nr, dtype=np.int32))
-        self.sv = None
+        super().__init__(src, prj, outdir, cwd=cwd, mode=mode, order=order, tweak=tweak, resume=resume,
+                         control=dict(reltol=1e-6, abstol=1e-6, init_step=1e-3),
+                         override=lambda k, d: dict(interval=INTERVALS[k % 2], binary=True, ascii=k % 3 == 0),
+                         flood=monitors and dict(path=os.path.join(str(outdir), "run.flood.csv"), riv_depth=0.0,
+                                                 riv_type=1))
         self.states = []
         self.qcur = []                                   # the integrator's order after each solver step
 
@@ -152,29 +116,15 @@ class Run:
             # at any tolerance (qcur 1 after each of 12 solver steps at 1e-4 and at 1e-6): 5 cm of ponded water on every
             # element gives it a transient to resolve, so the order rises and the split crosses a real history
             y0[:self.m.num_ele] += 0.05
-        self.sv = ShudSolver(self.h, y0, self.ctl)
-        return self
-
-    def restore(self, path):
-        self.sv = ShudSolver.resume(self.h, self.ctl, path, output=self.out, monitors=self.mon)
-        return self
-
-    def forcing(self, t, tout):
-        f = self.P.forcing(t, tout)
-        bc = self.P.bc_rows()
-        if bc:
-            self.h.set_step_inputs(step={}, bc_tables=bc)
-        return f
+        return super().start(y0)
 
     def steps(self, n, each=None):
-        def on_output(i, t, y):
+        def on_output(i, t, y):                          # (the flood monitor has run: ProjectRun.run)
             self.states.append(y.copy())
             self.qcur.append(self.sv.stats()["qcur"])
-            if self.mon is not None:
-                self.mon.flood(t)
             if each:
                 each(self)
-        self.sv.run(n, forcing=self.forcing, on_output=on_output, output=self.out)
+        self.run(n, on_output=on_output)
         return self
 
     def snapshot(self, path):
@@ -188,16 +138,6 @@ class Run:
         files = {os.path.basename(f): open(f, "rb").read() for f in sorted(glob.glob(os.path.join(self.outdir, "*")))
                  if not f.endswith(".ckpt")}
         return self.states, nc, st, files
-
-    def close(self):
-        if self.sv:
-            self.sv.close()
-        if self.out:
-            self.out.close()
-        if self.mon:
-            self.mon.close()
-        self.h.close()
-        self.sv = self.out = self.mon = None
 
 
 def _same(a, b):
@@ -470,9 +410,8 @@ def test_shud_gpu_checkpoint_resume(tmp_path):
     open(cfg, "w").write(txt)
 
     def run(outdir, extra, env=None):
-        cmd = ([SHUD_GPU, "-o", str(outdir), "-C", root, "-e", "0.125", "--flood", "--ic-snapshots"] + extra +
-               [src, "ccw"])
-        return subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ, **(env or {})))
+        return shud_gpu_run.run(["-o", outdir, "-C", root, "-e", "0.125", "--flood", "--ic-snapshots"] + extra +
+                                [src, "ccw"], env=env, check=False)
     a, b, ck = tmp_path / "straight", tmp_path / "split", str(tmp_path / "p.ckpt")
     r0 = run(a, ["-n", "6"])
     r1 = run(b, ["-n", "3", "--checkpoint", ck])

@@ -3,41 +3,24 @@
 A synthetic project in the reference's text formats (shud_rhs.synth.write_project: mesh, attributes, parameter
 tables, rivers, calibration, cfg.para / cfg.ic, forcing list + csv, LAI, MF) is run by
   * shud_gpu (C++: libshud_host readers/init/forcing + the device RHS, ET prelude, integrator and outputs), and
-  * the Python driver (ShudSolver + runtime.Output) over the same libshud_host project;
+  * the Python driver (shud_rhs.driver.ProjectRun: ShudSolver + runtime.Output) over the same libshud_host project;
 every .dat output must be byte-identical.  A hand-driven device run of the same loop is checked against the
 CPU oracle chain (oracle ET prelude + oracle RHS + oracle integrator, fed the C++ host's forcing rows) over the
 first hour, as tests/test_gpu_ode.py does for synthetic forcing: within 1e-6 of the solver's error weight
 (parity unpinned by the reference itself)."""
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle
-from conftest import PKG_DIR, assert_close
-from shud_rhs import abi, host, shudio, synth
+import shud_gpu_run
+from conftest import assert_close
+from shud_rhs import abi, driver, host, shudio, synth
 from shud_rhs import runtime as rt
-from shud_rhs.solver import SolverControl, ShudSolver
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
-LONLAT = {0: "FORCING_FIRST", 1: "FORCING_MEAN", 2: "FIXED"}
-
-
-def _ctl(c):
-    return SolverControl(reltol=c["reltol"], abstol=c["abstol"], init_step=c["init_step"], max_step=c["max_step"],
-                         et_step=c["et_step"], start=c["start_time"])
-
-
-def _device_model(P):
-    m = P.model()
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
-    h.et_attach(P.et_model())
-    h.et_set_state(P.array("y_is"), P.array("y_snow"))
-    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})      # shud_gpu.cpp: first updateforcing's u_satn
-    return m, h
 
 
 @pytest.mark.parametrize("case", ["plain", "bc_substep"])
@@ -52,39 +35,15 @@ def test_shud_gpu_matches_python_driver(tmp_path, case):
         synth.write_project(str(src), "syn", 2000, days=1.0, max_step=30.0, et_step=10.0, dt_out=60, bc=True,
                             cfg_output=True)
     out_c, out_p = tmp_path / "out_cpp", tmp_path / "out_py"
-    r = subprocess.run([SHUD_GPU, "-o", str(out_c), "-C", str(src), str(src), "syn"], capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = shud_gpu_run.run(["-o", out_c, "-C", src, src, "syn"])
     assert "RHS" in r.stdout
 
-    P = host.Project(str(src), "syn", cwd=str(src))
-    c = P.control()
-    m, h = _device_model(P)
-    sv = ShudSolver(h, P.array("y0"), _ctl(c))
-    h.prepare_outputs()
-    out = rt.Output(stream=h.stream())
-    os.makedirs(out_p)
-    decl = P.outputs(str(out_p))
-    for d in decl:
-        p, n = h.device_array(d["array"])
-        if d["column"] >= 0:
-            p += 8 * d["column"] * m.num_ele
-        out.add(d["basename"], p, d["n_all"], d["interval"], d["iflux"], start_time=c["forc_start_time"],
-                flag_io=d["flag_io"],
-                binary=bool(c["binary"]), ascii=bool(c["ascii"]), radiation_input_mode=c["radiation_input_mode"],
-                terrain_radiation=c["terrain_radiation"], solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]],
-                lon=c["solar_lon_deg"], lat=c["solar_lat_deg"])
-    def forcing(t, tout):                       # shud_gpu.cpp: forcing rows, then the BC rows, then ET
-        f = P.forcing(t, tout)
-        bc = P.bc_rows()
-        if bc:
-            h.set_step_inputs(step={}, bc_tables=bc)
-        return f
-
+    run = driver.ProjectRun(src, "syn", out_p, cwd=src).start()
+    P, c, m, decl = run.P, run.c, run.m, run.decl
     assert (len(P.bc_rows()) == 4) == (case == "bc_substep")
-    t, _ = sv.run(c["num_steps"], forcing=forcing, output=out)
+    t, _ = run.run()
     assert abs(t - c["end_time"]) < 1e-6
-    out.close()
+    run.out.close()
     files = sorted(os.path.basename(f) for f in glob.glob(str(out_c / "*.dat")))
     assert len(files) == len(decl) == 24
     assert files == sorted(os.path.basename(f) for f in glob.glob(str(out_p / "*.dat")))
@@ -99,17 +58,16 @@ def test_shud_gpu_matches_python_driver(tmp_path, case):
     if case == "plain":
         gw = shudio.read_dat(str(out_c / "syn.eleygw.dat"))["data"]
         assert np.abs(gw - P.array("y0")[2 * m.num_ele:3 * m.num_ele]).max() < 1.0    # one day moves gw < 1 m
-    sv.close()
-    h.close()
+    run.close()
 
 
 def test_device_loop_vs_oracle_chain_first_hour(tmp_path):
     synth.write_project(str(tmp_path), "syn", 2000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60)
     P = host.Project(str(tmp_path), "syn", cwd=str(tmp_path))
     c = P.control()
-    ctl = _ctl(c)
+    ctl = driver.solver_control(c)
     y0 = P.array("y0")
-    m, h = _device_model(P)
+    m, h = driver.device_model(P)
     etm = P.et_model()
     oe = oracle.OracleEt(etm)
     oe.set_state(P.array("y_is"), P.array("y_snow"))
@@ -153,14 +111,10 @@ def test_shud_gpu_rhs_partition_check(tmp_path, parts, lake):
     mesh, and compares every owned DY with the unpartitioned handle's: zero mismatched entries (bit-identical).
     lake: a project with one lake (200 lake elements); the owned state of the lake's rank carries the lake stage
     after its reaches ([sf|us|gw|riv|lake]) and the lake's DY is compared too."""
-    import json
     src = tmp_path / "in"
     synth.write_project(str(src), "syn", 30000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60, lake=lake)
-    r = subprocess.run([SHUD_GPU, "--rhs-check", str(parts), "--evals", "6", "-C", str(src), str(src), "syn"],
-                       capture_output=True, text=True, timeout=240)
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"shud_gpu_rhs_check"')]
-    assert r.returncode == 0 and line, r.stdout + r.stderr
-    res = json.loads(line[-1])["shud_gpu_rhs_check"]
+    res = shud_gpu_run.json_line(shud_gpu_run.run(["--rhs-check", parts, "--evals", "6", "-C", src, src, "syn"]),
+                                 "shud_gpu_rhs_check")
     assert res["parts"] == parts and res["evals"] == 6 and res["mismatched_entries"] == 0, res
     assert res["max_ghost_ele"] > 0 and res["imbalance"] < 1.05
 
@@ -169,13 +123,9 @@ def test_shud_gpu_rhs_partition_check(tmp_path, parts, lake):
 def test_shud_gpu_rhs_bench_single_rank(tmp_path, lake):
     """shud_gpu --rhs-bench with WORLD_SIZE = 1 (the N > 1 mode runs one process per GPU over RCCL); with a lake
     the device state holds the lake stage after the reaches."""
-    import json
     src = tmp_path / "in"
     synth.write_project(str(src), "syn", 30000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60, lake=lake)
-    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([SHUD_GPU, "--rhs-bench", "--evals", "20", "-o", str(tmp_path / "o"), "-C", str(src),
-                        str(src), "syn"], capture_output=True, text=True, timeout=240, env=env)
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"shud_gpu_rhs_bench"')]
-    assert r.returncode == 0 and line, r.stdout + r.stderr
-    res = json.loads(line[-1])["shud_gpu_rhs_bench"]
+    r = shud_gpu_run.run(["--rhs-bench", "--evals", "20", "-o", tmp_path / "o", "-C", src, src, "syn"],
+                         env=dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0"))
+    res = shud_gpu_run.json_line(r, "shud_gpu_rhs_bench")
     assert res["evals"] == 20 and res["exit_code"] == 0 and res["ms_per_eval"] > 0

@@ -13,29 +13,22 @@ tau / 1), so the .dat rows hold the very values the monitors read: stages bit fo
 A run without the flags writes none of the three files and the same .dat bytes; the written restart file loads as
 the .cfg.ic of a copy of the project."""
 import glob
-import json
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import mon_py
-from conftest import PKG_DIR
+import shud_gpu_run
 from shud_rhs import host, shudio, synth
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
 MON_FILES = ("syn.flood.csv", "syn.cfg.ic.update", "syn.cfg.ic.bak")
 
 
 def _run(src, out, *flags):
-    r = subprocess.run([SHUD_GPU, *flags, "-o", str(out), "-C", str(src), str(src), "syn"], capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout + r.stderr
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"shud_gpu"')]
-    return json.loads(line[-1])["shud_gpu"]
+    return shud_gpu_run.json_line(shud_gpu_run.run([*flags, "-o", out, "-C", src, src, "syn"]))
 
 
 @pytest.fixture(scope="module")

@@ -9,22 +9,19 @@
 import glob
 import os
 import re
-import subprocess
 import zipfile
 
 import numpy as np
 import pytest
 from scipy.io import netcdf_file
 
-from conftest import GOLDEN, PKG_DIR
-from shud_rhs import abi, host, shudio, synth
+import shud_gpu_run
+from conftest import GOLDEN
+from shud_rhs import driver, shudio, synth
 from shud_rhs import runtime as rt
-from shud_rhs.solver import ShudSolver, SolverControl
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
 HIST = "2000-01-01T00:00:00Z: created by SHUD"
-LONLAT = {0: "FORCING_FIRST", 1: "FORCING_MEAN", 2: "FIXED"}
 FILL_BITS = 0x7cf00000
 # +-0 (a -0 mean: a negative double that underflows), a float subnormal, underflow to 0, a round-to-even tie, overflow
 # to inf, +-inf, NaN
@@ -182,55 +179,12 @@ def _set_mode(indir, prj, base, mode, cfg_text="OUT_DIR ncout\n"):
 
 
 def _py_driver(indir, prj, cwd, outdir, end_day=-1.0, history=HIST):
-    """shud_gpu's set-up and loop in Python: ShudSolver + runtime.Output over the same libshud_host project"""
-    P = host.Project(str(indir), prj, cwd=str(cwd), end_day=end_day)
-    c, ncc = P.control(), P.ncoutput()
-    m = P.model()
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
-    h.et_attach(P.et_model())
-    h.et_set_state(P.array("y_is"), P.array("y_snow"))
-    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
-    sv = ShudSolver(h, P.array("y0"), SolverControl(reltol=c["reltol"], abstol=c["abstol"], init_step=c["init_step"],
-                                                    max_step=c["max_step"], et_step=c["et_step"], start=c["start_time"]))
-    h.prepare_outputs()
-    out = rt.Output(stream=h.stream())
-    os.makedirs(outdir, exist_ok=True)
-    mode = ncc["output_mode"]
-    n_of = {"ele": m.num_ele, "riv": m.num_riv, "lake": getattr(m, "num_lake", 0)}
-    if mode:
-        for kind, n in n_of.items():
-            if kind == "ele" or n > 0:
-                out.attach_nc(kind, n, c["forc_start_time"], out_dir=ncc["out_dir"] or None, history=history,
-                              crs_wkt=ncc["crs_wkt"] or None, mesh=P.mesh_nodes() if kind == "ele" else None)
-    decl = P.outputs(str(outdir))
-    for d in decl:
-        p, _ = h.device_array(d["array"])
-        if d["column"] >= 0:
-            p += 8 * d["column"] * m.num_ele
-        kind = None
-        if mode:
-            kind = next((k for k, n in n_of.items() if (k == "ele" or n > 0) and d["n_all"] == n), None)
-        out.add(d["basename"], p, d["n_all"], d["interval"], d["iflux"], start_time=c["forc_start_time"],
-                flag_io=d["flag_io"], binary=bool(c["binary"]) and mode != 1, ascii=bool(c["ascii"]) and mode != 1,
-                radiation_input_mode=c["radiation_input_mode"], terrain_radiation=c["terrain_radiation"],
-                solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"], lat=c["solar_lat_deg"],
-                nc=kind, legacy=mode != 1)
-
-    def forcing(t, tout):
-        f = P.forcing(t, tout)
-        bc = P.bc_rows()
-        if bc:
-            h.set_step_inputs(step={}, bc_tables=bc)
-        return f
-
-    if mode:
-        out.nc_begin()
-    sv.run(c["num_steps"], forcing=forcing, output=out)
-    out.close()
-    sv.close()
-    h.close()
-    info = dict(decl=decl, mesh=P.mesh_nodes(), ne=m.num_ele, nr=m.num_riv, nl=n_of["lake"])
-    P.close()
+    """shud_gpu's set-up and loop in Python (shud_rhs.driver) -> what the checks below read"""
+    run = driver.ProjectRun(indir, prj, outdir, cwd=cwd, end_day=end_day, history=history).start()
+    run.run()
+    m = run.m
+    info = dict(decl=run.decl, mesh=run.P.mesh_nodes(), ne=m.num_ele, nr=m.num_riv, nl=getattr(m, "num_lake", 0))
+    run.close()
     return info
 
 
@@ -294,11 +248,7 @@ def test_both_and_netcdf_modes_on_ccw(tmp_path):
 
 
 def _shud_gpu(args, history=HIST):
-    env = dict(os.environ)
-    env.pop("SHUD_NC_HISTORY", None)
-    if history is not None:
-        env["SHUD_NC_HISTORY"] = history
-    return subprocess.run([SHUD_GPU] + [str(a) for a in args], capture_output=True, text=True, timeout=240, env=env)
+    return shud_gpu_run.run(args, env={"SHUD_NC_HISTORY": history}, check=False)
 
 
 def test_shud_gpu_both_mode_synthetic(tmp_path):

@@ -9,7 +9,6 @@ Models: ccw, heihe, variant(3000, 5) (3024 elements) and variant(20000, 43) (200
 partial last tiles and both boundary kinds; each also under a seeded random permutation as the caller's numbering."""
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,14 +16,14 @@ import torch
 
 import cases
 import renumber as rn
+import shud_gpu_run
 import test_gpu_share as ts
-from conftest import GOLDEN, PKG_DIR
+from conftest import GOLDEN
 from print_ctrl_py import PrintCtrlPy
 from shud_rhs import abi
 from shud_rhs import runtime as rt
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
 
 MODES = [abi.SHUD_MODE_SERIAL, abi.SHUD_MODE_OMP]
 OMP_SKIPPED = ("q_es", "q_eu", "q_eg", "q_tu", "q_tg", "q_eta", "i_beta")       # as test_gpu_parity._compare_sequence
@@ -480,8 +479,8 @@ def _ccw_project(root):
 
 
 def _run_shud_gpu(root, src, outdir, extra, env=None):
-    cmd = [SHUD_GPU, "-q", "-o", str(outdir), "-C", str(root), "-e", "0.125", "--ic-snapshots"] + extra + [src, "ccw"]
-    return subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ, **(env or {})))
+    return shud_gpu_run.run(["-q", "-o", outdir, "-C", root, "-e", "0.125", "--ic-snapshots"] + extra + [src, "ccw"],
+                            env=env, check=False)
 
 
 def test_shud_gpu_reorder(tmp_path):

@@ -15,6 +15,7 @@ import pytest
 
 import cases
 import renumber as rn
+import shud_gpu_run
 import test_gpu_order as tgo
 import test_gpu_share as ts
 from shud_rhs import abi
@@ -185,8 +186,12 @@ def test_shud_gpu_reorder_tiles(tmp_path):
     root = str(tmp_path / "ref")
     src = tgo._ccw_project(root)
     a, b = tmp_path / "plain", tmp_path / "tiles"
-    ra = tgo._run_shud_gpu(root, src, a, [])
-    rb = tgo._run_shud_gpu(root, src, b, ["--reorder", "tiles"])
+
+    def run(outdir, extra, env=None):
+        return shud_gpu_run.run(["-q", "-o", outdir, "-C", root, "-e", "0.125", "--ic-snapshots"] + extra +
+                                [src, "ccw"], env=env, check=False)
+    ra = run(a, [])
+    rb = run(b, ["--reorder", "tiles"])
     assert ra.returncode == 0 and rb.returncode == 0, ra.stdout + ra.stderr + rb.stdout + rb.stderr
     files = sorted(os.path.basename(f) for f in glob.glob(str(a / "*.dat")))
     assert len(files) >= 15 and files == sorted(os.path.basename(f) for f in glob.glob(str(b / "*.dat")))
@@ -205,8 +210,8 @@ def test_shud_gpu_reorder_tiles(tmp_path):
     ub = np.array(open(b / "ccw.cfg.ic.update").read().split()[9:9 + 6 * 1147], dtype=np.float64)
     assert ua.size == ub.size == 6 * 1147
     assert np.all(np.abs(ua - ub) <= 2.0 * 13.1 * (1e-4 * np.abs(ua) + 1e-4) + 1e-6)
-    rn_ = tgo._run_shud_gpu(root, src, tmp_path / "bad", ["--reorder", "nonsense"])
+    rn_ = run(tmp_path / "bad", ["--reorder", "nonsense"])
     assert rn_.returncode != 0 and "bfs" in rn_.stderr and "tiles" in rn_.stderr and "nonsense" in rn_.stderr
     assert not os.path.exists(tmp_path / "bad")
-    rw = tgo._run_shud_gpu(root, src, tmp_path / "wb", ["--reorder", "tiles"], env={"SHUD_WB_DIAG": "1"})
+    rw = run(tmp_path / "wb", ["--reorder", "tiles"], env={"SHUD_WB_DIAG": "1"})
     assert rw.returncode != 0 and "--reorder cannot be combined with SHUD_WB_DIAG" in rw.stderr

@@ -38,7 +38,7 @@ def _device_run(case, layout, monkeypatch, tmp_path_factory):
     """drive one handle through the recorded schedule, once per (case, layout) -> dict(dir, decl, ic, wb rows ...)"""
     if (case, layout) in _DEV:
         return _DEV[(case, layout)]
-    from shud_rhs import runtime as rt
+    from shud_rhs import driver, runtime as rt
     monkeypatch.setenv("SHUD_RHS_PACKED", "1" if layout == "packed" else "0")
     L = rw.load(case, tmp_path_factory)
     rec, m, prj = L["rec"], L["m"], L["prj"]
@@ -46,32 +46,18 @@ def _device_run(case, layout, monkeypatch, tmp_path_factory):
     P = rw.project(L)
     c = P.control()
     NE, NR, NL = m.num_ele, m.num_riv, getattr(m, "num_lake", 0) or 0
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
+    _, h = driver.device_model(P, model=m)
     assert h.layout()["packed"] == (layout == "packed"), h.layout()
-    h.et_attach(P.et_model())
     h.et_set_state(rec["ic_is"], rec["ic_snow"])
     d_y, d_s, d_dy = (h.device_alloc(8 * m.num_y) for _ in range(3))
     h.h2d(d_s, L["y0"])
     h.summary(d_s)                                       # LoadIC / SetIC2Y: the arrays before the first f()
     h.prepare_outputs()
     out = rt.Output(stream=h.stream())
-    decl = [d for d in P.outputs(str(outdir)) if d["array"] not in rw.ARR_RN]
-    for d in decl:
-        p, n = h.device_array(d["array"])
-        assert p, d
-        if d["column"] >= 0:
-            p += 8 * d["column"] * NE
-        out.add(d["basename"], p, d["n_all"], d["interval"], d["iflux"], start_time=c["forc_start_time"],
-                flag_io=d["flag_io"], binary=bool(c["binary"]), ascii=bool(c["ascii"]), **rw.header_kw(c))
-    arr = lambda a: h.device_array(a)[0]                                       # noqa: E731
-    mon = rt.RunMonitors(stream=h.stream())
-    flood_path = outdir / f"{prj}.flood.csv"
-    mon.add_flood(flood_path, arr(abi.SHUD_ARR_Y_RIV_STG), arr(abi.SHUD_ARR_QRIV_DOWN), NR, m.riv["riv_depth"],
-                  P.riv_type())
-    ic_path = outdir / f"{prj}.cfg.ic.update"
-    mon.add_ic(ic_path, P.update_ic_step(), arr(abi.SHUD_ARR_Y_ELE_IS), arr(abi.SHUD_ARR_Y_ELE_SNOW),
-               arr(abi.SHUD_ARR_Y_ELE_SURF), arr(abi.SHUD_ARR_Y_ELE_UNSAT), arr(abi.SHUD_ARR_Y_ELE_GW),
-               arr(abi.SHUD_ARR_Y_RIV_STG), arr(abi.SHUD_ARR_Y_LAKE_STG) if NL else None, NE, NR, NL)
+    # rn_h / rn_t / rn_factor: a handle without a terrain-radiation ET step has nothing to put there
+    decl = driver.add_outputs(P, h, out, outdir, c=c, override=lambda k, d: None if d["array"] in rw.ARR_RN else {})
+    mon = driver.monitors(P, h, outdir, prj, flood=True, ic=True)
+    flood_path, ic_path = outdir / f"{prj}.flood.csv", outdir / f"{prj}.cfg.ic.update"
     ics = []
 
     def ic_update(t):                                    # PrintInit(Init_update, t): every written file is kept
@@ -82,8 +68,7 @@ def _device_run(case, layout, monkeypatch, tmp_path_factory):
     env = refio.WRITER_CASES[case]["env"]
     wb, wb_rows, wb_terms = None, [], []
     if env.get("SHUD_WB_DIAG"):
-        wb = rt.WaterBalance(h, P.wb_interval(), start_time=c["start_time"], forc_start_time=c["forc_start_time"],
-                             prefix=outdir / prj, **rw.header_kw(c))
+        wb = driver.water_balance(P, h, outdir, prj, c=c)
     # PrintInit at StartTime comes before any f(): the reference's arrays hold the initial condition as read, no
     # boundary head yet, which the device's summary arrays already carry.  As the host driver does (shud_gpu.cpp),
     # that first file is written from the host's arrays.

@@ -12,22 +12,19 @@ terms are exact."""
 import glob
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
 import ode_kernels_py
+import shud_gpu_run
 import wb_py
-from conftest import ATOL, PKG_DIR, RTOL
-from shud_rhs import abi, et, host, partition, shudio, synth, workload
+from conftest import ATOL, RTOL
+from shud_rhs import abi, driver, et, partition, shudio, synth, workload
 from shud_rhs import runtime as rt
-from shud_rhs.solver import ShudSolver, SolverControl
 
 pytestmark = pytest.mark.gpu
-SHUD_GPU = os.path.join(PKG_DIR, "shud_gpu")
-LONLAT = {0: "FORCING_FIRST", 1: "FORCING_MEAN", 2: "FIXED"}
 ARR4 = ["acc3", "accfull", "acc3_budget", "accfull_budget"]
 RES4 = ["resid3", "residfull", "resid3_budget", "residfull_budget"]
 
@@ -334,63 +331,18 @@ def test_write_errors_surface(tmp_path):
     rig.close()
 
 
-def _python_run(src, outdir, trapz, end_day=-1.0, use_wb=True):
-    P = host.Project(str(src), "syn", cwd=str(src), end_day=end_day)
-    c = P.control()
-    m = P.model()
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
-    h.et_attach(P.et_model())
-    h.et_set_state(P.array("y_is"), P.array("y_snow"))
-    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
-    sv = ShudSolver(h, P.array("y0"), SolverControl(reltol=c["reltol"], abstol=c["abstol"], init_step=c["init_step"],
-                                                    max_step=c["max_step"], et_step=c["et_step"],
-                                                    start=c["start_time"]))
-    h.prepare_outputs()
-    d_y0 = h.device_alloc(8 * m.num_y)
-    h.h2d(d_y0, P.array("y0"))
-    h.summary(d_y0)
-    out = rt.Output(stream=h.stream())
-    os.makedirs(outdir)
-    for d in P.outputs(str(outdir)):
-        p, n = h.device_array(d["array"])
-        if d["column"] >= 0:
-            p += 8 * d["column"] * m.num_ele
-        out.add(d["basename"], p, d["n_all"], d["interval"], d["iflux"], start_time=c["forc_start_time"],
-                flag_io=d["flag_io"], binary=bool(c["binary"]), ascii=bool(c["ascii"]),
-                radiation_input_mode=c["radiation_input_mode"], terrain_radiation=c["terrain_radiation"],
-                solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"], lat=c["solar_lat_deg"])
-    wb = None
-    if use_wb:
-        wb = rt.WaterBalance(h, P.wb_interval(), start_time=c["start_time"], trapz=trapz,
-                             prefix=os.path.join(str(outdir), "syn"), forc_start_time=c["forc_start_time"],
-                             radiation_input_mode=c["radiation_input_mode"],
-                             terrain_radiation=c["terrain_radiation"],
-                             solar_lonlat_mode=LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"],
-                             lat=c["solar_lat_deg"])
-
-    def forcing(t, tout):
-        f = P.forcing(t, tout)
-        bc = P.bc_rows()
-        if bc:
-            h.set_step_inputs(step={}, bc_tables=bc)
-        return f
-
-    t, _ = sv.run(c["num_steps"], forcing=forcing, output=out, wb=wb)
-    assert abs(t - c["end_time"]) < 1e-6
-    out.close()
-    if wb is not None:
-        wb.close()
-    h.device_free(d_y0)
-    sv.close()
-    h.close()
-    P.close()
+def _python_run(src, outdir, trapz, end_day=-1.0, quad=False):
+    """shud_rhs.driver's run with the diagnostics (quad: and the monitor) -> (monitor steps, integrator stats)"""
+    run = driver.ProjectRun(src, "syn", outdir, cwd=src, end_day=end_day, wb=True, trapz=trapz, quad=quad).start()
+    t, _ = run.run()
+    assert abs(t - run.c["end_time"]) < 1e-6
+    res = run.sv.quad_steps, run.sv.stats()
+    run.close()
+    return res
 
 
 def _shud_gpu(src, outdir, env, end_day=None):
-    cmd = [SHUD_GPU, "-o", str(outdir), "-C", str(src)] + (["-e", str(end_day)] if end_day else []) + [str(src), "syn"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ, **env))
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r
+    return shud_gpu_run.run(["-o", outdir, "-C", src] + (["-e", end_day] if end_day else []) + [src, "syn"], env=env)
 
 
 def _dat(d):
@@ -436,10 +388,7 @@ def test_driver_off_writes_no_diagnostic_files(tmp_path):
     src = tmp_path / "in"
     synth.write_project(str(src), "syn", 2000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60)
     _shud_gpu(src, tmp_path / "off", {"SHUD_WB_DIAG": "off"}, end_day=0.125)
-    env = {k: v for k, v in os.environ.items() if k != "SHUD_WB_DIAG"}
-    r = subprocess.run([SHUD_GPU, "-o", str(tmp_path / "unset"), "-C", str(src), "-e", "0.125", str(src), "syn"],
-                       capture_output=True, text=True, timeout=240, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
+    _shud_gpu(src, tmp_path / "unset", {"SHUD_WB_DIAG": None}, end_day=0.125)
     files = _dat(tmp_path / "off")
     assert len(files) == 24 and not set(WB_FILES) & set(files) and files == _dat(tmp_path / "unset")
     for f in files:

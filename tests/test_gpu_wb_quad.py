@@ -7,21 +7,20 @@ The seven rates are reductions: each is held to the bound every summation order 
 (wb_py.device_sum) bit for bit.  Qout is the sum of QrivDown as f() left it: its terms are copies, no cbrt.  Given
 the rates, the monitor step and the quad row are scalar IEEE operations in the reference's order (the library is
 built with -ffp-contract=off): accumulators, previous rates, rows and the file are compared bit for bit."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cases
 import oracle
+import shud_gpu_run
 import test_gpu_wb as tw
 import wb_py
 import wb_quad_py as qp
-from shud_rhs import abi, host, shudio, synth, workload
+from shud_rhs import abi, driver, host, shudio, synth, workload
 from shud_rhs import runtime as rt
-from shud_rhs.solver import ZERO, ShudSolver, SolverControl
+from shud_rhs.solver import ZERO
 
 pytestmark = pytest.mark.gpu
 QUAD_FILE = "syn" + qp.QUAD_EXT
@@ -291,55 +290,6 @@ def test_refused_handles_stay_refused(kind):
     tw.test_refusals(kind)
 
 
-def _python_run_quad(src, outdir, end_day):
-    """tests/test_gpu_wb.py's _python_run with the monitor: -> (monitor steps, integrator stats)"""
-    P = host.Project(str(src), "syn", cwd=str(src), end_day=end_day)
-    c = P.control()
-    m = P.model()
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
-    h.et_attach(P.et_model())
-    h.et_set_state(P.array("y_is"), P.array("y_snow"))
-    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
-    sv = ShudSolver(h, P.array("y0"), SolverControl(reltol=c["reltol"], abstol=c["abstol"], init_step=c["init_step"],
-                                                    max_step=c["max_step"], et_step=c["et_step"],
-                                                    start=c["start_time"]))
-    h.prepare_outputs()
-    d_y0 = h.device_alloc(8 * m.num_y)
-    h.h2d(d_y0, P.array("y0"))
-    h.summary(d_y0)
-    out = rt.Output(stream=h.stream())
-    os.makedirs(outdir)
-    hdr = dict(radiation_input_mode=c["radiation_input_mode"], terrain_radiation=c["terrain_radiation"],
-               solar_lonlat_mode=tw.LONLAT[c["solar_lonlat_mode"]], lon=c["solar_lon_deg"], lat=c["solar_lat_deg"])
-    for d in P.outputs(str(outdir)):
-        p, n = h.device_array(d["array"])
-        if d["column"] >= 0:
-            p += 8 * d["column"] * m.num_ele
-        out.add(d["basename"], p, d["n_all"], d["interval"], d["iflux"], start_time=c["forc_start_time"],
-                flag_io=d["flag_io"], binary=bool(c["binary"]), ascii=bool(c["ascii"]), **hdr)
-    wb = rt.WaterBalance(h, P.wb_interval(), start_time=c["start_time"], prefix=os.path.join(str(outdir), "syn"),
-                         forc_start_time=c["forc_start_time"], **hdr)
-    wb.quad_enable()
-
-    def forcing(t, tout):
-        f = P.forcing(t, tout)
-        bc = P.bc_rows()
-        if bc:
-            h.set_step_inputs(step={}, bc_tables=bc)
-        return f
-
-    t, _ = sv.run(c["num_steps"], forcing=forcing, output=out, wb=wb, quad=True)
-    assert abs(t - c["end_time"]) < 1e-6
-    out.close()
-    wb.close()
-    res = sv.quad_steps, sv.stats()
-    h.device_free(d_y0)
-    sv.close()
-    h.close()
-    P.close()
-    return res
-
-
 @pytest.mark.parametrize("case", ["plain", "bc_substep"])
 def test_drivers_byte_identical_with_quad(tmp_path, case):
     """shud_gpu under SHUD_WB_DIAG=1 SHUD_WB_DIAG_QUAD=1 against ShudSolver.run(wb=, quad=True) over the first six
@@ -352,11 +302,12 @@ def test_drivers_byte_identical_with_quad(tmp_path, case):
     else:
         synth.write_project(str(src), "syn", 2000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60)
     out_c, out_p = tmp_path / "out_cpp", tmp_path / "out_py"
-    r = tw._shud_gpu(src, out_c, {"SHUD_WB_DIAG": "1", "SHUD_WB_DIAG_QUAD": "1"}, 0.25)
+    r = shud_gpu_run.run(["-o", out_c, "-C", src, "-e", 0.25, src, "syn"],
+                         env={"SHUD_WB_DIAG": "1", "SHUD_WB_DIAG_QUAD": "1"})
     assert "not supported" not in r.stderr
-    line = json.loads([s for s in r.stdout.splitlines() if s.startswith('{"shud_gpu"')][-1])["shud_gpu"]
+    line = shud_gpu_run.json_line(r)
     assert line["quad_steps"] == line["cvode_steps"] > 6 and line["loop_phases_s"]["wb_quad"] > 0
-    steps, st = _python_run_quad(src, out_p, 0.25)
+    steps, st = tw._python_run(src, out_p, trapz=False, end_day=0.25, quad=True)
     assert steps == st["nst"] == line["cvode_steps"]
     files = tw._dat(out_c)
     assert len(files) == 30 and files == tw._dat(out_p) and set(tw.WB_FILES + [QUAD_FILE]) <= set(files)
@@ -385,12 +336,10 @@ def test_driver_quad_off_writes_no_quad_file(tmp_path, value):
     SHUD_WB_DIAG_QUAD=1 without SHUD_WB_DIAG is not read at all"""
     src = tmp_path / "in"
     synth.write_project(str(src), "syn", 2000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60)
-    base = {k: v for k, v in os.environ.items() if k not in ("SHUD_WB_DIAG", "SHUD_WB_DIAG_QUAD")}
+    base = {"SHUD_WB_DIAG": None, "SHUD_WB_DIAG_QUAD": None}
     for name, env, nfiles in (("on", dict(SHUD_WB_DIAG="1", **({} if value is None else {"SHUD_WB_DIAG_QUAD": value})),
                                29), ("nodiag", {"SHUD_WB_DIAG_QUAD": "1"}, 24)):
-        r = subprocess.run([tw.SHUD_GPU, "-o", str(tmp_path / name), "-C", str(src), "-e", "0.125", str(src), "syn"],
-                           capture_output=True, text=True, timeout=240, env=dict(base, **env))
-        assert r.returncode == 0, r.stdout + r.stderr
+        r = shud_gpu_run.run(["-o", tmp_path / name, "-C", src, "-e", "0.125", src, "syn"], env=dict(base, **env))
         files = tw._dat(tmp_path / name)
         assert len(files) == nfiles and QUAD_FILE not in files
         assert "wb_quad" not in r.stdout and "quad_steps" not in r.stdout
@@ -406,14 +355,9 @@ def test_quad_loop_vs_oracle_chain_first_hour(tmp_path):
     synth.write_project(str(tmp_path), "syn", 2000, days=1.0, max_step=10.0, et_step=60.0, dt_out=60)
     P = host.Project(str(tmp_path), "syn", cwd=str(tmp_path))
     c = P.control()
-    ctl = SolverControl(reltol=c["reltol"], abstol=c["abstol"], init_step=c["init_step"], max_step=c["max_step"],
-                        et_step=c["et_step"], start=c["start_time"])
+    ctl = driver.solver_control(c)
     y0 = P.array("y0")
-    m = P.model()
-    h = rt.RhsHandle(m, mode=abi.SHUD_MODE_SERIAL)
-    h.et_attach(P.et_model())
-    h.et_set_state(P.array("y_is"), P.array("y_snow"))
-    h.set_step_inputs(step={"u_satn": np.zeros(m.num_ele)})
+    m, h = driver.device_model(P)
     oe = oracle.OracleEt(P.et_model())
     oe.set_state(P.array("y_is"), P.array("y_snow"))
     r = oracle.OracleRhs(m, abi.SHUD_MODE_SERIAL)
