@@ -103,6 +103,12 @@ const double *shud_project_node_xy(shud_project_t p, int which, int64_t *n);
 const int32_t *shud_project_ele_nodes(shud_project_t p, int64_t *n);
 /* Riv[i].type of <prj>.sp.riv, 1-based as in the file (the Type column of <prj>.flood.csv); n = NumRiv */
 const int32_t *shud_project_riv_type(shud_project_t p, int64_t *n);
+/* a zone table for the zonal outputs (include/shud_out.h, shud_out_add_zonal): one SHUD table (TabularData layout:
+ * "nrow ncol", a header line, the rows) of NumEle rows with the columns index and zone; a zone id is an integer >= 0
+ * (0: the element is in no zone).  *zone: NumEle ids in the file's element numbering, owned by the project and valid
+ * until the next call; *n_zone: the largest id.  Non-zero with shud_project_error's message: a file that cannot be
+ * read, a row count that is not NumEle, an id that is not integral, a negative id. */
+int shud_project_zones(shud_project_t p, const char *path, const int32_t **zone, int32_t *n_zone);
 
 /* Per ET step [t, tout): updateAllTimeSeries(t) (movePointer of every forcing / LAI / MF series) and the
  * inputs of tReadForcing + ET for shud_et_step: the current station rows, LAI and MF rows, and the TSR

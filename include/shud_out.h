@@ -119,6 +119,56 @@ int shud_out_resume(shud_out_t o, int on);
  * d_src[col_src[c]], col_src host [n_all] with values in [0, n_all); flag_io and the header's column numbers are
  * still indexed by the caller's column c.  A create-time change: the export kernel already reads index lists. */
 int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *spec, const int32_t *col_src);
+/* Zonal controls: a print control that reduces its source to one value per zone BEFORE accumulating, so its state is
+ * n_zone doubles and n_zone * 8 bytes cross PCIe per interval.  At every shud_out_export, for each zone z = 1..n_zone:
+ *   members: the columns c with zone[c] == z, ascending c; term p_c = weight[c] * x_c (one IEEE multiplication, never
+ *   fused into an addition), or x_c without a weight; x_c = d_src[col_src ? col_src[c] : c];
+ *   S_z = the project's deterministic order (csrc/shud_reduce.h) over the zone's own term vector: block_partial over
+ *   chunks of 1024 consecutive members (0.0 past the last), then ordered_total over the zone's partials; an empty zone
+ *   has S_z = +0.0; buf_z += S_z.
+ * At the interval's end the row holds buf_z * (tau / NumUpdate) (SHUD_ZONE_SUM), or that product divided by
+ * W_z = the same ordered sum of the zone's weights, formed once at registration (SHUD_ZONE_WMEAN); then buf_z = 0.
+ * The file has NumVar = n_zone and icol = 1..n_zone; header, time stamps and interval rule are any control's. */
+enum { SHUD_ZONE_SUM = 0, SHUD_ZONE_WMEAN = 1 };
+typedef struct {
+    int32_t n_zone;              /* NZ >= 1                                                                  */
+    const int32_t *zone;         /* host, n_all ids in the caller's column numbering: 0 = in no zone, 1..NZ  */
+    const double *weight;        /* host, n_all weights by caller column; NULL = unweighted (SUM only)       */
+    int32_t op;                  /* SHUD_ZONE_SUM / SHUD_ZONE_WMEAN                                          */
+} ShudZoneSpec;
+/* registers a zonal control over spec->d_src (n_all values; col_src NULL or as in shud_out_add_mapped).  Refused with
+ * SHUD_ERR_ARG and nothing created: n_zone < 1, a zone id outside 0..NZ, a non-NULL spec->flag_io, WMEAN without a
+ * weight, WMEAN with an empty zone or a W_z that is zero or not finite, a col_src entry out of range.  Zonal controls
+ * have no NetCDF sink.  All zonal controls of a set share two launches per export; plain controls launch what they
+ * launch without them. */
+int shud_out_add_zonal(shud_out_t o, const ShudPrintSpec *spec, const int32_t *col_src, const ShudZoneSpec *zones);
+/* the create-time plan of shud_out_add_zonal as plain arrays, without a device (tests, tools): the member list (source
+ * indices, zone-major, ascending column within a zone) and the weights in member order [n_all each], zone_off
+ * [n_zone + 1], the chunk table (1-based zone and first member of every 1024-member chunk; [n_all / 1024 + n_zone + 1]
+ * each) and W_z [n_zone] (WMEAN).  Any output may be NULL.  Same refusals as shud_out_add_zonal. */
+int shud_zone_plan(int32_t n_all, const int32_t *col_src, const ShudZoneSpec *zones, int32_t *n_member, int32_t *member,
+                   double *weight, int32_t *zone_off, int32_t *n_chunk, int32_t *chunk_zone, int32_t *chunk_first,
+                   double *wsum);
+/* the ordered sum above of p[0..n) on the host (W_z is formed with it) */
+double shud_zone_order_sum(const double *p, int64_t n);
+/* the kernels an output set launches, and how many launches of each it has enqueued so far (every launch site of the
+ * set counts, the measurement entries included): what a run launches can be asserted without a profiler */
+enum {
+    SHUD_OUT_K_ACCUMULATE = 0,   /* k_accumulate: one per export, over the plain controls                    */
+    SHUD_OUT_K_SNAP,             /* k_snap: one per finished row of a control without a NetCDF sink          */
+    SHUD_OUT_K_SNAP_NC,          /* k_snap_nc / k_snap_nc_sel: one per finished row of a control with a sink */
+    SHUD_OUT_K_SNAP_NC_SEL,
+    SHUD_OUT_K_ZONE_PARTIAL,     /* k_zone_partial, k_zone_final: one each per export of a set with zonal controls */
+    SHUD_OUT_K_ZONE_FINAL,
+    SHUD_OUT_K_SNAP_WMEAN,       /* k_snap_wmean: one per finished row of a SHUD_ZONE_WMEAN control          */
+    SHUD_OUT_KERNELS
+};
+int shud_out_launches(shud_out_t o, int64_t counts[SHUD_OUT_KERNELS]);
+/* the kernel's name as it appears in a trace, NULL outside the enum */
+const char *shud_out_kernel_name(int which);
+/* measurement only (tools/zonal_bench.py): device time [ms] of one export's per-step pass, averaged over `reps` passes
+ * after a warm-up: which = 0 the two zonal launches, 1 k_accumulate over the plain controls.  The accumulators grow. */
+int shud_out_time_pass(shud_out_t o, int which, int reps, double *ms_pass);
 /* attaches the NetCDF file spec->kind describes (one per kind) to the output set; controls are then registered into
  * it with shud_out_add_nc.  Nothing is written yet; an OUT_DIR that exists and is no directory is refused here. */
 int shud_out_attach_nc(shud_out_t o, const ShudNcSpec *spec);

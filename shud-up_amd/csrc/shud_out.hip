@@ -42,6 +42,7 @@
 #include "shud_nc.h"
 #include "shud_out.h"
 #include "shud_reduce.h"
+#include "shud_zone.h"
 
 namespace {
 
@@ -63,6 +64,71 @@ __global__ void __launch_bounds__(256) k_snap(double *__restrict__ buf, double *
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         snap[i] = buf[i] * f;
+        buf[i] = 0.0;
+    }
+}
+
+// ---- zonal controls (shud_out_add_zonal): the source reduced to one value per zone before it is accumulated ----------
+// Plan (shud_zone.cpp): the members of every zone are contiguous in `member` (source indices) with their weights beside
+// them in the same order, cut into chunks of 1024; a zone's partials are contiguous in `part`.  Two launches per export
+// for every zonal control of the set (blockIdx.y = control), in shud_reduce.h's order and without atomics.
+struct ZoneSlot {                        // one zonal control on the device (POD, copied to a device table)
+    const double *src;
+    const int *member;                   // [n_member]
+    const double *weight;                // [n_member] in member order; nullptr = unweighted
+    const int *chunk_zone, *chunk_first; // [n_chunk]
+    const int *zone_off, *zone_chunk;    // [nz + 1] member / chunk offsets of zone z (0-based)
+    const int *multi;                    // [n_multi] zones of more than one chunk
+    double *part;                        // [n_chunk]
+    double *buf;                         // [nz]
+    int n_chunk, nz, n_multi;
+};
+
+// one block per chunk: lane l holds weight * x of member chunk_first + l (one multiplication; the build has no
+// contraction), 0.0 past the zone's end; block_partial stores part[chunk]
+__global__ void __launch_bounds__(shud::red::kRedThreads) k_zone_partial(const ZoneSlot *__restrict__ slots) {
+    const ZoneSlot s = slots[blockIdx.y];
+    const int b = blockIdx.x;
+    if (b >= s.n_chunk) return;                                  // the whole block: the grid is the set's widest control
+    const int first = s.chunk_first[b];
+    const int end = min(first + shud::kZoneChunk, s.zone_off[s.chunk_zone[b] + 1]);
+    const int i = first + (int)threadIdx.x;
+    double v[1] = {0.0};
+    if (i < end) {
+        const double x = s.src[s.member[i]];
+        v[0] = s.weight ? s.weight[i] * x : x;
+    }
+    shud::red::block_partial<1>(v, 0u, s.part, s.n_chunk);
+}
+
+// buf_z += S_z.  Blocks 0 .. n_multi-1: ordered_total over the partials of one zone of several chunks.  The blocks after
+// them take 1024 zones each, a thread per zone of at most one chunk: ordered_total over one partial p is 0.0 + p (acc[0]
+// of lane 0 starts from the identity, so a -0.0 partial gives +0.0; every later addend is +0.0), and over none +0.0.
+__global__ void __launch_bounds__(shud::red::kFinThreads) k_zone_final(const ZoneSlot *__restrict__ slots) {
+    __shared__ double sm[shud::red::kFinThreads / 64];
+    const ZoneSlot s = slots[blockIdx.y];
+    const int b = blockIdx.x;
+    if (b < s.n_multi) {
+        const int z = s.multi[b];
+        const int c0 = s.zone_chunk[z];
+        const double t = shud::red::ordered_total(s.part + c0, s.zone_chunk[z + 1] - c0, false, sm);
+        if (threadIdx.x == 0) s.buf[z] += t;
+        return;
+    }
+    const int z = (b - s.n_multi) * shud::red::kFinThreads + (int)threadIdx.x;
+    if (z >= s.nz) return;
+    const int c0 = s.zone_chunk[z], nc = s.zone_chunk[z + 1] - c0;
+    if (nc > 1) return;
+    const double t = nc ? 0.0 + s.part[c0] : 0.0;
+    s.buf[z] += t;
+}
+
+// the interval's end of a SHUD_ZONE_WMEAN control: k_snap's product, divided by W_z
+__global__ void __launch_bounds__(256) k_snap_wmean(double *__restrict__ buf, double *__restrict__ snap,
+                                                    const double *__restrict__ wsum, int n, double f) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        snap[i] = (buf[i] * f) / wsum[i];
         buf[i] = 0.0;
     }
 }
@@ -171,6 +237,11 @@ struct PrintCtrl {
     bool legacy = true;                  // a .dat / .csv is written too: the double snapshot is formed and copied
     uint32_t *d_slab = nullptr, *h_slab[2] = {nullptr, nullptr};
     int *d_col = nullptr;
+    // zonal control (shud_out_add_zonal): the operation (-1: a plain control), the plan's integer tables (one
+    // allocation), the weights in member order, the chunk partials and W_z (WMEAN)
+    int zone_op = -1;
+    int *d_zint = nullptr;
+    double *d_zweight = nullptr, *d_zpart = nullptr, *d_zwsum = nullptr;
 };
 
 struct OutTask {                         // one row of one control: (bank, control, left endpoint of the interval)
@@ -188,10 +259,15 @@ struct shud_out {
     bool copy_pending = false;           // a snapshot copy is in flight (the next snapshot waits for it)
     int bank = 0;
     std::vector<PrintCtrl> pc;
-    std::vector<PrintSlot> slots;        // host mirror of d_slots, index-aligned with pc
+    std::vector<PrintSlot> slots;        // host mirror of d_slots: the plain controls, in registration order
     PrintSlot *d_slots = nullptr;
     int n_slots_alloc = 0;
     int max_nvar = 0;
+    std::vector<ZoneSlot> zslots;        // host mirror of d_zslots: the zonal controls, in registration order
+    ZoneSlot *d_zslots = nullptr;
+    int n_zslots_alloc = 0;
+    int max_zchunk = 0, max_zfin = 0;    // grid widths of k_zone_partial / k_zone_final
+    int64_t n_launch[SHUD_OUT_KERNELS] = {};   // launches enqueued so far, per kernel (shud_out_launches)
     // writer threads: writer w owns the controls k with k % kWriters == w
     std::thread writer[kWriters];
     std::mutex mu;
@@ -292,7 +368,9 @@ extern "C" int shud_out_create(int device, void *stream, shud_out_t *out) {
 // Print_Ctrl::Init / InitIJ (Model_Control.cpp:759-858) + open_file (:683-758)
 // col_src (NULL: identity): caller column c reads d_src[col_src[c]]; flag_io and the header's icol stay by caller column
 // nc_kind >= 0: a NetCDF sink in the attached file of that kind; legacy = false: no .dat / .csv beside it
-static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src, int nc_kind = -1, bool legacy = true) {
+// zp: the plan of a zonal control (op zone_op): NumVar = zp->nz columns 1..nz, no column selection
+static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src, int nc_kind = -1, bool legacy = true,
+                   const shud::ZonePlan *zp = nullptr, int zone_op = -1) {
     if (!o || !s || !s->basename || !s->d_src) return shud_fail(SHUD_ERR_ARG, "null argument");
     if (nc_kind >= 0 && (nc_kind >= SHUD_NC_KINDS || !o->nc[nc_kind]))
         return shud_fail(SHUD_ERR_ARG, "Print_Ctrl %s: no NetCDF file of kind %d attached (shud_out_attach_nc)",
@@ -313,12 +391,13 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src,
     p.numall = s->n_all;
     p.tau = s->iflux ? 1440. : 1.;
     std::vector<int> sel;
-    for (int i = 0; i < s->n_all; i++) {
+    for (int i = 0; i < s->n_all && !zp; i++) {
         if (s->flag_io && !s->flag_io[i]) continue;
         sel.push_back(col_src ? col_src[i] : i);
         p.icol.push_back((double)(i + 1));                       // icol[k] = (double)(i + 1)
     }
-    p.numvar = (int)sel.size();
+    for (int k = 0; zp && k < zp->nz; k++) p.icol.push_back((double)(k + 1));
+    p.numvar = (int)p.icol.size();
     if (p.numvar <= 0) fprintf(stderr, "WARNING: Empty columns in %s.\n;", p.filename.c_str());
     p.legacy = legacy;
     if (nc_kind >= 0) {                                              // Netcdf*VarSink::onInit
@@ -350,7 +429,33 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src,
             HIP_TRY(hipMemcpy(p.d_col, col.data(), nq * sizeof(int), hipMemcpyHostToDevice));
         }
     }
-    if (col_src || (s->flag_io && p.numvar < s->n_all)) {
+    ZoneSlot zs{};
+    if (zp) {
+        // the plan's integer tables in one allocation, in this order
+        const std::vector<int> *tab[6] = {&zp->member, &zp->chunk_zone, &zp->chunk_first, &zp->zone_off, &zp->zone_chunk,
+                                          &zp->multi};
+        std::vector<int> all;
+        size_t at[6];
+        for (int k = 0; k < 6; k++) {
+            at[k] = all.size();
+            all.insert(all.end(), tab[k]->begin(), tab[k]->end());
+        }
+        const size_t nch = zp->chunk_zone.size();
+        HIP_TRY(hipMalloc(&p.d_zint, std::max(all.size(), (size_t)1) * sizeof(int)));
+        HIP_TRY(hipMemcpy(p.d_zint, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&p.d_zpart, std::max(nch, (size_t)1) * sizeof(double)));
+        if (!zp->weight.empty()) {
+            HIP_TRY(hipMalloc(&p.d_zweight, zp->weight.size() * sizeof(double)));
+            HIP_TRY(hipMemcpy(p.d_zweight, zp->weight.data(), zp->weight.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        if (zone_op == SHUD_ZONE_WMEAN) {
+            HIP_TRY(hipMalloc(&p.d_zwsum, zp->wsum.size() * sizeof(double)));
+            HIP_TRY(hipMemcpy(p.d_zwsum, zp->wsum.data(), zp->wsum.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        p.zone_op = zone_op;
+        zs = ZoneSlot{s->d_src, p.d_zint + at[0], p.d_zweight, p.d_zint + at[1], p.d_zint + at[2], p.d_zint + at[3],
+                      p.d_zint + at[4], p.d_zint + at[5], p.d_zpart, p.d_buf, (int)nch, zp->nz, (int)zp->multi.size()};
+    } else if (col_src || (s->flag_io && p.numvar < s->n_all)) {
         HIP_TRY(hipMalloc(&p.d_sel, nb * sizeof(int)));
         HIP_TRY(hipMemcpy(p.d_sel, sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -417,9 +522,23 @@ static int out_add(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src,
             csv_preamble(p.fa);
         }
     }
+    o->pc.push_back(p);
+    if (zp) {
+        o->max_zchunk = std::max(o->max_zchunk, zs.n_chunk);
+        o->max_zfin = std::max(o->max_zfin, zs.n_multi + (zs.nz + shud::red::kFinThreads - 1) / shud::red::kFinThreads);
+        o->zslots.push_back(zs);
+        if ((int)o->zslots.size() > o->n_zslots_alloc) {
+            if (o->d_zslots) HIP_TRY(hipFree(o->d_zslots));
+            o->n_zslots_alloc = std::max(16, 2 * (int)o->zslots.size());
+            HIP_TRY(hipMalloc(&o->d_zslots, o->n_zslots_alloc * sizeof(ZoneSlot)));
+        }
+        HIP_TRY(hipMemcpyAsync(o->d_zslots, o->zslots.data(), o->zslots.size() * sizeof(ZoneSlot), hipMemcpyHostToDevice,
+                               o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        return SHUD_OK;
+    }
     o->max_nvar = std::max(o->max_nvar, p.numvar);
     o->slots.push_back(PrintSlot{s->d_src, p.d_sel, p.d_buf, p.numvar});
-    o->pc.push_back(p);
     // the device slot table (tiny): re-uploaded whole on every add
     if ((int)o->slots.size() > o->n_slots_alloc) {
         if (o->d_slots) HIP_TRY(hipFree(o->d_slots));
@@ -436,6 +555,45 @@ extern "C" int shud_out_add(shud_out_t o, const ShudPrintSpec *s) { return out_a
 extern "C" int shud_out_add_mapped(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src) {
     if (!col_src) return shud_fail(SHUD_ERR_ARG, "shud_out_add_mapped: null col_src");
     return out_add(o, s, col_src);
+}
+
+extern "C" int shud_out_add_zonal(shud_out_t o, const ShudPrintSpec *s, const int32_t *col_src, const ShudZoneSpec *z) {
+    if (!o || !s || !s->basename || !s->d_src || !z) return shud_fail(SHUD_ERR_ARG, "null argument");
+    if (s->flag_io)
+        return shud_fail(SHUD_ERR_ARG, "Print_Ctrl %s: flag_io is not for a zonal control (zone 0 leaves a column out)",
+                         s->basename);
+    shud::ZonePlan plan;
+    const int rc = shud::zone_plan(s->basename, s->n_all, col_src, z, &plan);
+    if (rc) return rc;
+    return out_add(o, s, nullptr, -1, true, &plan, z->op);
+}
+
+// the per-export pass of the zonal controls: every chunk's partial, then every zone's total into its accumulator
+static void launch_zonal(shud_out *o) {
+    o->n_launch[SHUD_OUT_K_ZONE_PARTIAL]++;
+    o->n_launch[SHUD_OUT_K_ZONE_FINAL]++;
+    hipLaunchKernelGGL(k_zone_partial, dim3((unsigned)std::max(o->max_zchunk, 1), (unsigned)o->zslots.size()),
+                       dim3(shud::red::kRedThreads), 0, o->stream, o->d_zslots);
+    hipLaunchKernelGGL(k_zone_final, dim3((unsigned)std::max(o->max_zfin, 1), (unsigned)o->zslots.size()),
+                       dim3(shud::red::kFinThreads), 0, o->stream, o->d_zslots);
+}
+static void launch_accumulate(shud_out *o) {
+    o->n_launch[SHUD_OUT_K_ACCUMULATE]++;
+    const int gx = std::min((o->max_nvar + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_accumulate, dim3(gx, (unsigned)o->slots.size()), dim3(256), 0, o->stream, o->d_slots);
+}
+
+extern "C" int shud_out_time_pass(shud_out_t o, int which, int reps, double *ms_pass) {
+    if (!o || !ms_pass || reps < 1 || which < 0 || which > 1) return shud_fail(SHUD_ERR_ARG, "bad argument");
+    if (which == 0 ? o->zslots.empty() : (o->slots.empty() || o->max_nvar <= 0))
+        return shud_fail(SHUD_ERR_ARG, "shud_out_time_pass: the set has no %s control", which == 0 ? "zonal" : "plain");
+    HIP_TRY(hipSetDevice(o->device));
+    if (out_drain(o)) return out_report(o);
+    return shud::time_passes(o->stream, reps, [&]() -> int {
+        if (which == 0) launch_zonal(o); else launch_accumulate(o);
+        HIP_TRY(hipGetLastError());
+        return SHUD_OK;
+    }, ms_pass);
 }
 
 // NetCDF sinks: NetcdfOutputContext's three files (NetcdfOutputContext.cpp:1155-1175) and setSink (MD_initialize.cpp:
@@ -474,6 +632,7 @@ extern "C" int shud_out_nc_begin(shud_out_t o) {
 
 static void launch_snap_nc(shud_out *o, PrintCtrl &p, double f) {
     const int nquad = (p.numall + 3) / 4;
+    o->n_launch[p.d_col ? SHUD_OUT_K_SNAP_NC_SEL : SHUD_OUT_K_SNAP_NC]++;
     if (p.d_col)
         hipLaunchKernelGGL(k_snap_nc_sel, dim3((nquad + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap,
                            p.d_slab, p.d_col, nquad, f);
@@ -505,9 +664,12 @@ extern "C" int shud_out_export(shud_out_t o, double t) {
         const int rc = shud_out_nc_begin(o);
         if (rc) return rc;
     }
-    if (o->max_nvar > 0) {
-        const int gx = std::min((o->max_nvar + 255) / 256, 2048);
-        hipLaunchKernelGGL(k_accumulate, dim3(gx, (unsigned)o->pc.size()), dim3(256), 0, o->stream, o->d_slots);
+    if (o->max_nvar > 0) {                                       // the plain controls only
+        launch_accumulate(o);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!o->zslots.empty()) {
+        launch_zonal(o);
         HIP_TRY(hipGetLastError());
     }
     // OUTPUT_TRIGGER_EPSILON = 0.001 min (:939)
@@ -532,7 +694,12 @@ extern "C" int shud_out_export(shud_out_t o, double t) {
         PrintCtrl &p = o->pc[r.ctrl];
         const double f = p.tau / p.num_update;
         if (p.numvar <= 0) continue;
-        if (p.nc_ctrl < 0) {
+        if (p.zone_op == SHUD_ZONE_WMEAN) {
+            o->n_launch[SHUD_OUT_K_SNAP_WMEAN]++;
+            hipLaunchKernelGGL(k_snap_wmean, dim3((p.numvar + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap,
+                               p.d_zwsum, p.numvar, f);
+        } else if (p.nc_ctrl < 0) {
+            o->n_launch[SHUD_OUT_K_SNAP]++;
             hipLaunchKernelGGL(k_snap, dim3((p.numvar + 255) / 256), dim3(256), 0, o->stream, p.d_buf, p.d_snap,
                                p.numvar, f);
         } else {
@@ -570,6 +737,17 @@ extern "C" int shud_out_export(shud_out_t o, double t) {
     }
     o->cv.notify_all();
     return SHUD_OK;
+}
+
+extern "C" int shud_out_launches(shud_out_t o, int64_t counts[SHUD_OUT_KERNELS]) {
+    if (!o || !counts) return shud_fail(SHUD_ERR_ARG, "null argument");
+    for (int k = 0; k < SHUD_OUT_KERNELS; k++) counts[k] = o->n_launch[k];
+    return SHUD_OK;
+}
+extern "C" const char *shud_out_kernel_name(int which) {
+    static const char *name[SHUD_OUT_KERNELS] = {"k_accumulate", "k_snap", "k_snap_nc", "k_snap_nc_sel", "k_zone_partial",
+                                                 "k_zone_final", "k_snap_wmean"};
+    return which >= 0 && which < SHUD_OUT_KERNELS ? name[which] : nullptr;
 }
 
 extern "C" int shud_out_flush(shud_out_t o) {
@@ -636,6 +814,26 @@ int shud_out_ckpt_host(shud_out *o, CkptAr &a, bool check_only) {
             p.rows = rows;
         }
     }
+    // zonal controls: a trailer after the per-control fields, written only by a set that has one (so the section of a
+    // set without them is what it always was): a tag, then every control's operation (-1: plain)
+    static const char kZoneTag[8] = {'Z', 'O', 'N', 'A', 'L', 'O', 'P', '1'};
+    bool zonal = false;
+    for (int k = 0; k < n; k++) zonal = zonal || o->pc[k].zone_op >= 0;
+    if (zonal) {
+        char tag[8];
+        memcpy(tag, kZoneTag, 8);
+        a.raw(tag, 8);
+        if (a.load && (!a.ok || memcmp(tag, kZoneTag, 8) != 0))
+            return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field zone_op is missing: the checkpoint's output set has "
+                                           "no zonal control, this one has");
+        for (int k = 0; k < n; k++)
+            if (!a.same(o->pc[k].zone_op))
+                return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field zone_op of output control %d (%s) differs", k,
+                                 o->pc[k].filename.c_str());
+    } else if (a.load && a.ok && a.pos + 8 <= a.buf.size() && memcmp(a.buf.data() + a.pos, kZoneTag, 8) == 0) {
+        return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: field zone_op differs: the checkpoint's output set has zonal "
+                                       "controls, this one has none");
+    }
     if (!a.ok) return shud_fail(SHUD_ERR_ARG, "shud_ckpt_restore: section out.host is too short");
     if (a.load && !check_only)
         for (int k = 0; k < n; k++) {
@@ -676,6 +874,10 @@ extern "C" int shud_out_destroy(shud_out_t o) {
         if (p.d_sel) (void)hipFree(p.d_sel);
         if (p.d_slab) (void)hipFree(p.d_slab);
         if (p.d_col) (void)hipFree(p.d_col);
+        if (p.d_zint) (void)hipFree(p.d_zint);
+        if (p.d_zweight) (void)hipFree(p.d_zweight);
+        if (p.d_zpart) (void)hipFree(p.d_zpart);
+        if (p.d_zwsum) (void)hipFree(p.d_zwsum);
         for (int b = 0; b < 2; b++) {
             if (p.h_buf[b]) (void)hipHostFree(p.h_buf[b]);
             if (p.h_slab[b]) (void)hipHostFree(p.h_slab[b]);
@@ -685,6 +887,7 @@ extern "C" int shud_out_destroy(shud_out_t o) {
     for (int k = 0; k < SHUD_NC_KINDS; k++)                  // a file with no record is still written, with 0 records
         if (o->nc[k] && shud_nc_close(o->nc[k]) && !nrc) nrc = shud_fail(SHUD_ERR_ARG, "shud_out: %s", shud_nc_last_error());
     if (o->d_slots) (void)hipFree(o->d_slots);
+    if (o->d_zslots) (void)hipFree(o->d_zslots);
     if (o->ev_snap) (void)hipEventDestroy(o->ev_snap);
     for (int b = 0; b < 2; b++)
         if (o->ev_copied[b]) (void)hipEventDestroy(o->ev_copied[b]);

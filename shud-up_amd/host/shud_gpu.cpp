@@ -2,7 +2,7 @@
 // prelude, the integrator and the outputs on one MI355X, driven through the C-ABIs of include/.
 //
 //   shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots] [--reorder bfs|tiles]
-//            [--checkpoint PATH [--checkpoint-every N]] [--resume PATH] <input_dir> <project>
+//            [--checkpoint PATH [--checkpoint-every N]] [--resume PATH] [--zones FILE] <input_dir> <project>
 //   shud_gpu --rhs-check K | --rhs-bench [--evals N] ...   partitioned RHS modes (shud_gpu_part.cpp)
 //
 // input_dir/<project>.* are the reference's input files (FileIn, IO.cpp:53-91); forcing csv paths in
@@ -77,7 +77,7 @@ static constexpr double kZero = 1.0e-10;          // ZERO (Macros.hpp:32)
 static void usage() {
     fprintf(stderr, "usage: shud_gpu [-o outdir] [-e end_day] [-n num_steps] [-C cwd] [-q] [--flood] [--ic-snapshots]\n"
                     "                [--reorder bfs|tiles] [--checkpoint PATH [--checkpoint-every N]] [--resume PATH]\n"
-                    "                <input_dir> <project>\n"
+                    "                [--zones FILE] <input_dir> <project>\n"
                     "       shud_gpu --rhs-check K | --rhs-bench [--evals N] [-o outdir] [-C cwd] <input_dir> <project>\n"
                     "  --flood         write <outdir>/<project>.flood.csv (reaches above their bank after each solver step)\n"
                     "  --ic-snapshots  write <outdir>/<project>.cfg.ic.bak and, every Update_IC_STEP minutes and at the\n"
@@ -88,6 +88,10 @@ static void usage() {
                     "  --resume PATH   continue from a checkpoint into the same outdir: -n and -e count from the original\n"
                     "                  start, the files are cut back to the checkpoint and end up those of one straight run.\n"
                     "                  Neither with SHUD_WB_DIAG nor with OUTPUT_MODE NETCDF | BOTH.\n"
+                    "  --zones FILE    a zone table (NumEle rows: index, zone; 0 = in no zone): every element output also gets\n"
+                    "                  <outdir>/<project>.zone.<name> with one column per zone, reduced on the device at every\n"
+                    "                  step: the zone's sum for eleq* (m3/day), the area-weighted mean for every other one.\n"
+                    "                  Legacy files only: not with OUTPUT_MODE NETCDF.\n"
                     "  --reorder ORDER run the device side in a planned element order (neighbours close in memory);\n"
                     "                  every file stays in the input's element numbering.  Not with SHUD_WB_DIAG or lakes.\n"
                     "                  tiles: breadth-first pockets that each fill one 256-element sharing tile;\n"
@@ -120,7 +124,7 @@ static const char *lonlat_name(int m) { return m == 1 ? "FORCING_MEAN" : (m == 2
 // main() returns it as it did before: nothing is torn down on a failure path.
 struct Run {
     // ---- the command line ----
-    std::string outdir, cwd, reorder, ckpt_path, resume_path;
+    std::string outdir, cwd, reorder, ckpt_path, resume_path, zones_path;
     const char *indir = nullptr, *prj = nullptr;
     double end_day = -1.0;
     long long max_steps = -1, ckpt_every = 0;
@@ -211,6 +215,7 @@ int Run::parse_args(int argc, char **argv) {
         else if (a == "--checkpoint" && i + 1 < argc) ckpt_path = argv[++i];
         else if (a == "--checkpoint-every" && i + 1 < argc) ckpt_every = atoll(argv[++i]);
         else if (a == "--resume" && i + 1 < argc) resume_path = argv[++i];
+        else if (a == "--zones" && i + 1 < argc) zones_path = argv[++i];
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else pos.push_back(argv[i]);
     }
@@ -334,6 +339,11 @@ int Run::add_outputs() {
                         "reopen path, so a resumed run could not continue it\n", mode_name[ncc.output_mode]);
         return 1;
     }
+    if (!zones_path.empty() && ncc.output_mode == 1) {
+        fprintf(stderr, "--zones cannot be combined with OUTPUT_MODE NETCDF: the zonal outputs are legacy files "
+                        "(.dat / .csv), which that mode does not write\n");
+        return 1;
+    }
     // --resume: the controls keep the files of the run that wrote the checkpoint (cut back at the restore below)
     if (!resume_path.empty()) shud_out_resume(out, 1);
     if (ncc.output_mode != 0) {
@@ -384,6 +394,36 @@ int Run::add_outputs() {
             return 1;
         }
         nprint++;
+    }
+    // ---- --zones: the zonal twin of every element control (shud_rhs/driver.py: add_zonal_outputs) ----
+    if (!zones_path.empty()) {
+        const int32_t *zone = nullptr;
+        int32_t nz = 0;
+        if (shud_project_zones(p, zones_path.c_str(), &zone, &nz)) {
+            fprintf(stderr, "--zones: %s\n", shud_project_error());
+            return 1;
+        }
+        // the weights by the file's element numbering, like the zone ids: element c is the internal inv[c]
+        std::vector<double> area((size_t)mesh.num_ele);
+        for (int k = 0; k < mesh.num_ele; k++) area[(size_t)k] = mesh.area[inv.empty() ? k : inv[(size_t)k]];
+        for (const auto &d : decl) {
+            if (!arr_is_ele(d.array) || d.n_all != mesh.num_ele) continue;
+            const double *src = shud_rhs_device_array(h, d.array, nullptr);
+            if (d.column >= 0) src += (size_t)d.column * mesh.num_ele;
+            const std::string base(d.basename);
+            const size_t dot = base.rfind('.');
+            const std::string leaf = base.substr(dot + 1), name = base.substr(0, dot) + ".zone." + leaf;
+            const bool total = leaf.compare(0, 4, "eleq") == 0;
+            ShudPrintSpec ps = {name.c_str(), src, d.n_all, nullptr, d.interval, d.iflux, (int64_t)c.forc_start_time,
+                                c.binary, c.ascii, c.radiation_input_mode, c.terrain_radiation,
+                                lonlat_name(c.solar_lonlat_mode), c.solar_lon_deg, c.solar_lat_deg};
+            ShudZoneSpec zs = {nz, zone, total ? nullptr : area.data(), total ? SHUD_ZONE_SUM : SHUD_ZONE_WMEAN};
+            if (shud_out_add_zonal(out, &ps, inv.empty() ? nullptr : inv.data(), &zs)) {
+                fprintf(stderr, "shud_out_add_zonal(%s): %s\n", name.c_str(), shud_rhs_last_error_string());
+                return 1;
+            }
+            nprint++;
+        }
     }
     // the NetCDF headers and fixed variables (the mesh): before the time loop, not inside its first export
     if (ncc.output_mode != 0 && shud_out_nc_begin(out)) return fail("shud_out_nc_begin");
@@ -638,6 +678,12 @@ void Run::time_loop() {
 int Run::report() {
     shud_rhs_synchronize(h);
     const double loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop0).count();
+    // what the output set launched (include/shud_out.h: shud_out_launches), for the machine-readable line
+    int64_t launches[SHUD_OUT_KERNELS] = {};
+    shud_out_launches(out, launches);
+    std::string launch_txt;
+    for (int k = 0; k < SHUD_OUT_KERNELS; k++)
+        launch_txt += std::string(k ? ", \"" : "\"") + shud_out_kernel_name(k) + "\": " + std::to_string((long long)launches[k]);
     shud_out_destroy(out);
     long long flood_rows = 0;
     double mon_writer_s = 0.0;
@@ -686,10 +732,10 @@ int Run::report() {
            "\"rhs_evals\": %lld, \"newton_iters\": %lld, \"krylov_iters\": %lld, \"outputs\": %d, "
            "\"wall_s\": %.4f, \"loop_s\": %.4f, \"loop_phases_s\": {\"forcing\": %.4f, \"et_step\": %.4f, "
            "\"cvode\": %.4f, \"summary_diag\": %.4f, \"export\": %.4f, \"wb_diag\": %.4f%s%s}, \"host_syncs\": %lld, "
-           "%s%s\"exit\": %d}}\n",
+           "%s%s\"out_launches\": {%s}, \"exit\": %d}}\n",
            mesh.num_ele, t, nsteps, (long long)st.nst, (long long)(st.nfe + st.nfe_ls), (long long)st.nni,
            (long long)st.nli, nprint, wall, loop_s, ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], quad_txt, mon_txt,
-           (long long)st.n_sync, quad_n, mon_n, rc);
+           (long long)st.n_sync, quad_n, mon_n, launch_txt.c_str(), rc);
     shud_ode_destroy(ode);
     shud_rhs_device_free(h, d_y);
     if (d_du) shud_rhs_device_free(h, d_du);

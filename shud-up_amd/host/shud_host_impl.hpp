@@ -47,6 +47,7 @@ struct Project {
     double solar_lon_fixed = -9999.0, solar_lat_fixed = -9999.0;
     int update_ic_step = 1440;                   // UpdateICStep (Model_Control.hpp:181)
     std::vector<int32_t> riv_type;               // Riv[i].type, 1-based
+    std::vector<int32_t> zones;                  // the last table shud_project_zones read
 
     int NE = 0, NR = 0, NS = 0, NL = 0, NumNode = 0, NumLC = 0;
     // mesh SoA (ShudMeshSoA), params (ShudParamsSoA), ET statics (ShudEtMeshSoA)

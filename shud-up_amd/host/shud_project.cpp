@@ -732,6 +732,33 @@ const int32_t *shud_project_riv_type(shud_project_t h, int64_t *n) {
     return p.riv_type.data();
 }
 
+int shud_project_zones(shud_project_t h, const char *path, const int32_t **zone, int32_t *n_zone) {
+    if (!h || !path || !zone || !n_zone) return fail(nullptr, "null argument");
+    Project &p = *reinterpret_cast<Project *>(h);
+    *zone = nullptr;
+    *n_zone = 0;
+    Table t;
+    int rc = read_table_file(p, path, t);
+    if (rc) return rc;
+    if (t.ncol < 2) return fail(&p, "Fatal Error: zone table %s has %d columns (index, zone)", path, t.ncol);
+    if (t.nrow != p.NE)
+        return fail(&p, "Fatal Error: zone table %s has %d rows, NumEle = %d", path, t.nrow, p.NE);
+    std::vector<int32_t> z((size_t)p.NE);
+    int32_t nz = 0;
+    for (int i = 0; i < p.NE; i++) {
+        const double v = t.x[(size_t)i * t.ncol + 1];
+        if (!(v == floor(v)) || fabs(v) > 2147483647.0)
+            return fail(&p, "Fatal Error: zone table %s, row %d: zone %g is not an integer", path, i + 1, v);
+        if (v < 0) return fail(&p, "Fatal Error: zone table %s, row %d: zone %g is negative", path, i + 1, v);
+        z[(size_t)i] = (int32_t)v;
+        nz = std::max(nz, z[(size_t)i]);
+    }
+    p.zones.swap(z);
+    *zone = p.zones.data();
+    *n_zone = nz;
+    return 0;
+}
+
 int shud_project_mesh(shud_project_t h, ShudMeshSoA *m, ShudParamsSoA *q) {
     if (!h || !m || !q) return fail(nullptr, "null argument");
     Project &p = *reinterpret_cast<Project *>(h);

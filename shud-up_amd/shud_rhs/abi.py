@@ -236,7 +236,26 @@ class ShudPrintSpec(C.Structure):
                 ("solar_lonlat_mode", C.c_char_p), ("solar_lon_deg", C.c_double), ("solar_lat_deg", C.c_double)]
 
 
+SHUD_ZONE_SUM, SHUD_ZONE_WMEAN = 0, 1
+SHUD_OUT_KERNELS = 7
+
+
+class ShudZoneSpec(C.Structure):
+    _fields_ = [("n_zone", C.c_int32), ("zone", c_int32_p), ("weight", c_double_p), ("op", C.c_int32)]
+
+
+# the device-free plan unit behind shud_out_add_zonal (declared in include/shud_out.h)
+ZONE_FUNCTIONS = {
+    "shud_zone_plan": (C.c_int, [C.c_int32, c_int32_p, C.POINTER(ShudZoneSpec), c_int32_p, c_int32_p, c_double_p,
+                                 c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
+    "shud_zone_order_sum": (C.c_double, [c_double_p, C.c_int64]),
+}
+
 OUT_FUNCTIONS = {
+    "shud_out_add_zonal": (C.c_int, [_H, C.POINTER(ShudPrintSpec), c_int32_p, C.POINTER(ShudZoneSpec)]),
+    "shud_out_time_pass": (C.c_int, [_H, C.c_int, C.c_int, c_double_p]),
+    "shud_out_launches": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "shud_out_kernel_name": (C.c_char_p, [C.c_int]),
     "shud_rhs_summary": (C.c_int, [_H, C.c_void_p]),
     "shud_rhs_refresh_diagnostics": (C.c_int, [_H]),
     "shud_rhs_prepare_outputs": (C.c_int, [_H]),
@@ -432,7 +451,8 @@ def bind(lib, strict=True):
     for name, (res, args) in (list(FUNCTIONS.items()) + list(ET_FUNCTIONS.items()) + list(ODE_FUNCTIONS.items())
                               + list(OUT_FUNCTIONS.items()) + list(WB_FUNCTIONS.items())
                               + list(MON_FUNCTIONS.items()) + list(ORDER_FUNCTIONS.items())
-                              + list(NC_FUNCTIONS.items()) + list(CKPT_FUNCTIONS.items())):
+                              + list(NC_FUNCTIONS.items()) + list(CKPT_FUNCTIONS.items())
+                              + list(ZONE_FUNCTIONS.items())):
         if not strict and not hasattr(lib, name):
             continue
         f = getattr(lib, name)

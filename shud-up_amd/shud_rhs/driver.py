@@ -110,6 +110,50 @@ def add_outputs(P, h, out, outdir, c=None, ncc=None, history=None, override=None
     return decl
 
 
+def add_zonal_outputs(P, h, out, outdir, zones, c=None, ncc=None, override=None):
+    """the zonal twins (shud_gpu --zones): every element control of P.outputs(outdir) (NumEle columns of a per-element
+    array) also gets <outdir>/<prj>.zone.<leaf> with the same interval, iflux and binary / ascii settings, one column
+    per zone.  A leaf that begins with "eleq" (m3/day) is the zone's sum; every other one (eley*, elev*, rn_*) the mean
+    weighted by element area.  zones: a table's path (Project.zones) or NumEle ids in the file's numbering (0: in no
+    zone); on an ordered handle they go through the same inverse permutation as the element controls.  The twins cover
+    every element whatever io_ele masks, and are legacy files only: refused under OUTPUT_MODE NETCDF.
+    override(k, d): add_outputs' (None leaves the twin out too; only interval, binary and ascii are taken).
+    -> the registered twins' basenames"""
+    c = P.control() if c is None else c
+    ncc = P.ncoutput() if ncc is None else ncc
+    if ncc["output_mode"] == 1:
+        raise ValueError("zonal outputs are legacy files (.dat / .csv): not with OUTPUT_MODE NETCDF")
+    ne = _sizes(h.model)[0]
+    zone = P.zones(zones)[0] if isinstance(zones, (str, os.PathLike)) else np.asarray(zones)
+    if zone.shape != (ne,):
+        raise ValueError(f"zones: {zone.shape} ids, mesh {ne} elements")
+    nz = int(zone.max(initial=0))
+    area = np.asarray(h.model.ele["area"], dtype=np.float64)
+    inv = h.order()[2] if h.ordered else None
+    names = []
+    for k, d in enumerate(P.outputs(outdir)):
+        if d["array"] in ARR_NOT_ELE or d["n_all"] != ne:
+            continue
+        kw = dict(interval=d["interval"], binary=bool(c["binary"]), ascii=bool(c["ascii"]))
+        if override:
+            change = override(k, d)
+            if change is None:
+                continue
+            kw.update({key: v for key, v in change.items() if key in kw})
+        p, _ = h.device_array(d["array"])
+        if not p:
+            raise ValueError(f"no device source for {d['basename']}")
+        if d["column"] >= 0:
+            p += 8 * d["column"] * ne
+        head, leaf = d["basename"].rsplit(".", 1)
+        total = leaf.startswith("eleq")
+        out.add_zonal(f"{head}.zone.{leaf}", p, ne, kw.pop("interval"), d["iflux"], zone, n_zone=nz,
+                      weight=None if total else area, op="sum" if total else "mean", col_src=inv,
+                      start_time=c["forc_start_time"], **header_kw(c), **kw)
+        names.append(f"{head}.zone.{leaf}")
+    return names
+
+
 def water_balance(P, h, outdir, prj, trapz=False, quad=False, c=None):
     """WaterBalanceDiag::enable (shud.cpp:70-75), after the pre-loop summary; quad: SHUD_WB_DIAG_QUAD's monitor"""
     c = P.control() if c is None else c
@@ -170,11 +214,12 @@ class ProjectRun:
     """shud_gpu's run in Python: the stages above in shud_gpu's order, then start() or restore(path), run(), close().
     control: SolverControl overrides; override, history: add_outputs'; wb / trapz / quad: SHUD_WB_DIAG,
     SHUD_WB_DIAG_TRAPZ, SHUD_WB_DIAG_QUAD; flood, ic: monitors' (flood(t) then runs after every solver step's export);
-    resume: the outputs and monitors keep the files of an earlier run, for restore()."""
+    resume: the outputs and monitors keep the files of an earlier run, for restore(); zones: add_zonal_outputs' (a
+    table's path or NumEle ids): the zonal twins of the element controls, registered after them."""
 
     def __init__(self, indir, prj, outdir, cwd=None, end_day=-1.0, mode=abi.SHUD_MODE_SERIAL, order=None, tweak=None,
                  control=None, history=None, override=None, wb=False, trapz=False, quad=False, flood=False, ic=False,
-                 resume=False):
+                 resume=False, zones=None):
         self.prj, self.outdir, self.quad, self.flood = prj, str(outdir), quad, bool(flood)
         self.P = self.h = self.out = self.wb = self.mon = self.sv = None
         try:
@@ -189,6 +234,8 @@ class ProjectRun:
             if resume:
                 self.out.resume()
             self.decl = add_outputs(P, self.h, self.out, self.outdir, c=c, history=history, override=override)
+            self.zonal = [] if zones is None else add_zonal_outputs(P, self.h, self.out, self.outdir, zones, c=c,
+                                                                    override=override)
             if wb:
                 self.wb = water_balance(P, self.h, self.outdir, prj, trapz=trapz, quad=quad, c=c)
             if flood or ic:

@@ -62,6 +62,7 @@ def lib():
             "shud_project_wb_interval": (C.c_int, [_H]),
             "shud_project_update_ic_step": (C.c_int, [_H]),
             "shud_project_riv_type": (C.POINTER(C.c_int32), [_H, C.POINTER(C.c_int64)]),
+            "shud_project_zones": (C.c_int, [_H, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]),
             "shud_project_ncoutput": (C.c_int, [_H, C.POINTER(ShudNcOutputCfg)]),
             "shud_project_node_xy": (C.POINTER(C.c_double), [_H, C.c_int, C.POINTER(C.c_int64)]),
             "shud_project_ele_nodes": (C.POINTER(C.c_int32), [_H, C.POINTER(C.c_int64)]),
@@ -108,6 +109,11 @@ class Project:
         c = ShudControl()
         lib().shud_project_control(self.h, C.byref(c))
         return {k: getattr(c, k) for k, _ in ShudControl._fields_}
+
+    def num_ele(self):
+        m, q = abi.ShudMeshSoA(), abi.ShudParamsSoA()
+        lib().shud_project_mesh(self.h, C.byref(m), C.byref(q))
+        return m.num_ele
 
     def array(self, name):
         n = C.c_int64()
@@ -176,6 +182,15 @@ class Project:
         p = lib().shud_project_riv_type(self.h, C.byref(n))
         a = _arr(p, n.value, np.int32)
         return np.zeros(0, dtype=np.int32) if a is None else a
+
+    def zones(self, path):
+        """a zone table (shud_project_zones): NumEle rows of index, zone -> (zone ids [NumEle] in the file's element
+        numbering, 0 = in no zone; NZ = the largest id)"""
+        z, nz = C.POINTER(C.c_int32)(), C.c_int32()
+        if lib().shud_project_zones(self.h, str(path).encode(), C.byref(z), C.byref(nz)):
+            raise RuntimeError(f"shud_project_zones: {lib().shud_project_error().decode(errors='replace')}")
+        ne = self.num_ele()
+        return _arr(z, ne, np.int32), nz.value
 
     def ncoutput(self):
         """OUTPUT_MODE (0 LEGACY, 1 NETCDF, 2 BOTH) and the parsed NCOUTPUT_CFG: dict(output_mode, ncoutput_cfg,

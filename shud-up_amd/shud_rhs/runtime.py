@@ -487,6 +487,53 @@ class Output:
         self._keep.append((bn, sm, flags))
         return len(self._keep) - 1
 
+    def add_zonal(self, basename, d_src, n_all, interval, iflux, zone, weight=None, op="sum", col_src=None,
+                  start_time=0, flag_io=None, binary=True, ascii=False, radiation_input_mode=0, terrain_radiation=0,
+                  solar_lonlat_mode="FORCING_FIRST", lon=0.0, lat=0.0, nc=None, n_zone=None):
+        """a zonal control (shud_out_add_zonal): zone [n_all] ids by caller column (0: in no zone, 1..NZ), weight
+        [n_all] or None, op "sum" (the zone's ordered sum) or "mean" (the weighted mean; needs weight); the file has
+        NZ = n_zone (default: the largest id) columns.  col_src and the header keywords are add()'s.  flag_io and nc
+        are refused: zone 0 leaves a column out, and a zonal control has no NetCDF sink."""
+        if op not in ("sum", "mean"):
+            raise ValueError(f"op {op!r}: 'sum' or 'mean'")
+        if nc is not None:
+            # refused here: the C call has no way to ask for a sink
+            raise ShudRhsError(abi.SHUD_ERR_ARG, f"Output.add_zonal({basename}): nc = {nc!r}: a zonal control has no "
+                                                 "NetCDF sink")
+        zid = np.ascontiguousarray(zone, dtype=np.int32)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        cmap = None if col_src is None else np.ascontiguousarray(col_src, dtype=np.int32)
+        flags = None if flag_io is None else np.ascontiguousarray(flag_io, dtype=np.int32)
+        for name, a in (("zone", zid), ("weight", w), ("col_src", cmap), ("flag_io", flags)):
+            if a is not None and a.size != int(n_all):
+                raise ValueError(f"{name}: {a.size} values, n_all = {int(n_all)}")
+        nz = int(zid.max(initial=0)) if n_zone is None else int(n_zone)
+        bn, sm = str(basename).encode(), str(solar_lonlat_mode).encode()
+        spec = abi.ShudPrintSpec(bn, C.c_void_p(d_src), int(n_all), None if flags is None else flags.ctypes.data,
+                                 int(interval), int(iflux), int(start_time), int(bool(binary)), int(bool(ascii)),
+                                 int(radiation_input_mode), int(terrain_radiation), sm, float(lon), float(lat))
+        zs = abi.ShudZoneSpec(nz, zid.ctypes.data_as(abi.c_int32_p),
+                              None if w is None else w.ctypes.data_as(abi.c_double_p),
+                              abi.SHUD_ZONE_SUM if op == "sum" else abi.SHUD_ZONE_WMEAN)
+        _check(lib().shud_out_add_zonal(self.h, C.byref(spec), None if cmap is None else
+                                        cmap.ctypes.data_as(abi.c_int32_p), C.byref(zs)), "shud_out_add_zonal")
+        self._keep.append((bn, sm, None))
+        return len(self._keep) - 1
+
+    def launches(self):
+        """{kernel name: launches the set has enqueued so far} (shud_out_launches)"""
+        n = (C.c_int64 * abi.SHUD_OUT_KERNELS)()
+        _check(lib().shud_out_launches(self.h, n), "shud_out_launches")
+        return {lib().shud_out_kernel_name(k).decode(): int(n[k]) for k in range(abi.SHUD_OUT_KERNELS)}
+
+    def time_pass(self, which, reps):
+        """device ms of one export's per-step pass (shud_out_time_pass): which = "zonal" (the two zonal launches) or
+        "plain" (k_accumulate over the plain controls); the accumulators grow"""
+        ms = C.c_double()
+        _check(lib().shud_out_time_pass(self.h, {"zonal": 0, "plain": 1}[which], int(reps), C.byref(ms)),
+               "shud_out_time_pass")
+        return ms.value
+
     def attach_nc(self, kind, n_all, forc_start_time, out_dir=None, history=None, crs_wkt=None, mesh=None):
         """attach the NetCDF file of `kind` ("ele", "riv", "lake"; include/shud_nc.h) for add(nc=kind).  out_dir: OUT_DIR
         of the ncoutput cfg (None: beside the legacy files); history: the whole `history` attribute (None: "<UTC now>:
